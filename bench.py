@@ -12,7 +12,14 @@ under torch.distributed.run the ranks come from the environment.  The model is l
 rank 0 and broadcast as a blob over RCCL; each rank evaluates its own 2^20 batch
 (`--split weak`, the default) or its contiguous shard of one global 2^20 batch
 (`--split strong`, SURVEY §8(e): 2^17 per GPU at N = 8).  No collective touches the data
-path; timing is max over ranks.  A weak run also reports the strong split beside it.
+path; timing is max over ranks.
+
+A plain run sets up, warms up, times exactly --steps steps and prints its line.  --full adds
+everything measured beside the headline: the CPU baseline, the secondary lines (the other
+precisions, sizes, layouts and kernels, the native C++ callers) and, at N > 1, the strong
+split beside a weak run.  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md §5 for how roofline/cpu_baseline are
 derived; profiles/ holds the rocprofv3 summaries these numbers are checked against.
@@ -62,9 +69,16 @@ def parse(argv=None):
                     help="device array layout: tiled [B/256][n][256] (rigidbody_batch.h *_tiled entry points, "
                          "the headline) or plain SoA rows [n][B] (reported as a secondary line)")
     ap.add_argument("--rotate-gib", type=float, default=1.25, help="device memory the input sets span")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also measure the CPU baseline and the secondary lines (other "
+                         "precisions, sizes, layouts and kernels, the native callers; at N > 1 the strong splits). "
+                         "Off by default: a plain run sets up, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the output arrays of "
+                         "its launch as [n, B] rows, float32 / float64 as --dtype) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work budget of the baseline sample")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the side lines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the side lines")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the timed batches rotate over (1 = strictly serial launches, the "
                          "headline; the overlapped 2-stream rate is reported under 'secondary')")
@@ -75,7 +89,10 @@ def parse(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="CPU rehearsal of the launch / rank / reporting plumbing (gloo, no kernels, "
                          "no GPU); the JSON line says data='stub'")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.stub and a.dump_outputs:
+        ap.error("--dump-outputs writes what the kernels computed: not with --stub")
+    return a
 
 
 # ------------------------------------------------------------------ rank spawning
@@ -477,11 +494,39 @@ def per_rank(r, world, dev):
     return [{"rank": k, "wall_s": w, "kernel_ms_avg": km, "steps": int(st)} for k, (w, km, st) in enumerate(rows)]
 
 
+DUMP_MAX_BYTES = 63 * 1000 * 1000  # --dump-outputs: array bytes over all files and ranks (< 64 MB with the headers)
+OUT_NAMES = {"rnea": ("tau",), "fd": ("qdd",), "rnea_fd": ("tau", "qdd")}
+
+
+def dump_outputs(outs, kernel, layout, B, out_dir, max_bytes, suffix=""):
+    """--dump-outputs: the output arrays of one launch to out_dir/<name><suffix>.npy (tau for
+    rnea, qdd for fd, both for rnea_fd) in the launch's dtype, as [n, B] rows: a tiled output
+    [ceil(B/256), n, 256] is put back in configuration order and its last tile's padding
+    lanes, which no launch writes, are dropped.  Outputs larger than max_bytes in all are cut
+    to a fixed sample of configurations (sorted columns drawn with seed chains.SEED, the same
+    columns for every array and every run).  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols = None
+    per_col = sum(t.shape[-2] * t.element_size() for t in outs)
+    if per_col * B > max_bytes:
+        cols = np.sort(np.random.default_rng(chains.SEED).choice(B, max(1, max_bytes // per_col), replace=False))
+    shapes = {}
+    for name, t in zip(OUT_NAMES[kernel], outs):
+        x = t.cpu().numpy()
+        if layout == "tiled":
+            x = x.transpose(1, 0, 2).reshape(x.shape[1], -1)[:, :B]
+        x = np.ascontiguousarray(x if cols is None else x[:, cols])
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), x)
+        shapes[name + suffix] = list(x.shape)
+    return shapes
+
+
 def measure(mb, kernel, dt_name, B, layout, steps, warmup, world, rotate_gib, seed, spinup_ms=300.0, streams=1,
-            sync_every=0, graph=False, extra_streams=(), dev=None):
+            sync_every=0, graph=False, extra_streams=(), dev=None, dump=None):
     """Time `steps` launches of `kernel` over batches of B resident configurations (steps=None:
     a budget of ~SIDE_TARGET_MS of launches, budget_steps).  Returns a dict (wall,
-    kernel_ms_avg, bytes, sets, steps) plus the graph-replay figures if asked."""
+    kernel_ms_avg, bytes, sets, steps) plus the graph-replay figures if asked.  dump = (dir,
+    max bytes, file-name suffix): the outputs of the last timed launch go to dump_outputs."""
     ds = DT[dt_name]
     es = 4 if dt_name == "f32" else 8
     ns = nsets_for(mb.n, B, es, kernel, rotate_gib)
@@ -493,6 +538,8 @@ def measure(mb, kernel, dt_name, B, layout, steps, warmup, world, rotate_gib, se
         steps = int(rdist.max_over_ranks([budget_steps(launch)], world, dev)[0]) if world > 1 else budget_steps(launch)
     wall, km = time_launches(launch, steps, warmup, world, spinup_ms, streams, sync_every)
     r = {"wall": wall, "kernel_ms_avg": km, "bytes": set_bytes(mb.n, B, es, kernel), "sets": ns, "steps": steps}
+    if dump:  # timed step i ran on set i % ns; time_launches ended in a synchronize
+        r["dumped"] = dump_outputs(sets[(steps - 1) % ns][1], kernel, layout, B, *dump)
     if graph:
         gw, gkm, gl = time_graph(launch, steps)
         r.update({"graph_wall": gw, "graph_kernel_ms_avg": gkm, "graph_launches": gl})
@@ -1019,8 +1066,9 @@ def main(a):
         r = stub_measure(B, a.steps)
         kpath = "stub"
     else:
+        dump = (a.dump_outputs, DUMP_MAX_BYTES // world, f"_rank{rank}" if world > 1 else "") if a.dump_outputs else None
         r = measure(mb, a.kernel, a.dtype, B, a.layout, a.steps, a.warmup, world, a.rotate_gib, seed, a.spinup_ms,
-                    a.streams, a.sync_every)
+                    a.streams, a.sync_every, dump=dump)
         kpath = mb.kernel_path(a.kernel, a.dtype == "f64", B, a.layout == "tiled")
     ranks = per_rank(r, world, dev)
     wall, kern_ms = rdist.max_over_ranks([r["wall"], r["kernel_ms_avg"]], world, dev)
@@ -1073,8 +1121,10 @@ def main(a):
             line["reference_formulation"] = ref
     if world > 1:
         line["per_rank"] = ranks
+    if "dumped" in r:
+        line["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": r["dumped"]}
     sec = {}
-    if world > 1 and not strong:
+    if a.full and world > 1 and not strong:
         # the same global 2^20 batch sharded across the ranks, beside the weak line.
         # Its own launch budget (>= SIDE_MIN_LAUNCHES, ~SIDE_TARGET_MS, the same count on every
         # rank): at N = 8 a 2^17 fp64 shard is ~7 us, so the driver's --steps 20 would time
@@ -1122,12 +1172,12 @@ def main(a):
                       "the rank's shard), max over ranks; graph_*: the same launches replayed from a HIP graph "
                       "on every rank (device-bound), max over ranks",
             "status": "measured by the driver's N > 1 runs; our 1-GPU leases cannot run it (DESIGN.md §6)"}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.stub:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.stub:
         line["cpu_baseline"] = cpu_baseline(n, a.kernel, a.cpu_seconds)
     elif world > 1:
         line["cpu_baseline_note"] = ("not measured at world > 1: the CPU baseline runs on rank 0 of the 1-GPU "
-                                     "run only (bench.py --gpus 1), so the ranks' host cores stay idle here")
-    if rank == 0 and not a.no_secondary and world == 1 and n == 7 and not a.stub:
+                                     "run only (bench.py --gpus 1 --full), so the ranks' host cores stay idle here")
+    if a.full and rank == 0 and not a.no_secondary and world == 1 and n == 7 and not a.stub:
         r2 = measure(mb, a.kernel, a.dtype, a.batch, a.layout, None, 5, 1, a.rotate_gib, seed, 50.0, 2)
         sec[f"{a.kernel}_{a.dtype}_{a.layout}_2streams"] = {
             "evals_per_s": a.batch * r2["steps"] / r2["wall"], "step_ms_device": r2["kernel_ms_avg"],

@@ -28,7 +28,8 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.parametrize("split", ["weak", "strong"])
 def test_gpus2_spawns_two_ranks(split):
-    compact, line = _run("--gpus", "2", "--split", split)
+    # the strong splits beside a weak line are measured under --full only
+    compact, line = _run("--gpus", "2", "--split", split, *(["--full"] if split == "weak" else []))
     for k in REQUIRED:
         assert k in compact, k
     assert compact["n_gpus"] == 2 and compact["value"] == line["value"]
@@ -71,6 +72,63 @@ def test_single_rank_default():
     assert line["n_gpus"] == 1 and line["scaling"] == "weak"
     assert compact["config"]["workload"] == line["config"]["workload"] == "rnea_fr3_f64_tiled_b1048576"
     assert compact["roofline"]["bound"] == "hbm" and compact["roofline"]["unit"] == "GB/s"
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full a run measures its headline only: no strong split beside a weak N > 1 line
+    (nor, at N = 1, the CPU baseline and the secondary lines, which --full gates the same way);
+    --full is off by default and --dump-outputs, which writes kernel outputs, refuses --stub."""
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse(["--stub", "--dump-outputs", "d"])
+    compact, line = _run("--gpus", "2")
+    assert "secondary" not in line and "secondary" not in compact and "cpu_baseline" not in line
+    assert line["steps"] == 5 and line["ms_per_step"] > 0 and line["scaling"] == "weak"
+
+
+@pytest.mark.parametrize("layout", ["tiled", "soa"])
+def test_dump_outputs_layout_and_sample(tmp_path, layout):
+    """bench.dump_outputs on host tensors: [n, B] rows in configuration order from either layout
+    (a tiled output's padding lanes dropped), the launch's dtype kept; past the byte budget, the
+    same sorted seeded columns of every array, the same on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    n, B = 7, 600  # 3 tiles, the last one 88 configurations
+    want = [np.arange(n * B, dtype=np.float64).reshape(n, B) + 0.5 * k for k in range(2)]
+
+    def as_layout(x):
+        if layout == "soa":
+            return torch.as_tensor(x)
+        pad = np.full((n, 3 * 256), np.nan)
+        pad[:, :B] = x
+        return torch.as_tensor(np.ascontiguousarray(pad.reshape(n, 3, 256).transpose(1, 0, 2)))
+
+    outs = [as_layout(x) for x in want]
+    shapes = bench.dump_outputs(outs, "rnea_fd", layout, B, str(tmp_path / "all"), bench.DUMP_MAX_BYTES)
+    assert shapes == {"tau": [n, B], "qdd": [n, B]}
+    for name, w in zip(("tau", "qdd"), want):
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float64
+        np.testing.assert_array_equal(got, w)
+    # 100 configurations of both arrays fit in the budget: 100 sorted columns, the same twice
+    budget = 100 * 2 * n * 4
+    for d in ("s1", "s2"):
+        bench.dump_outputs([t.float() for t in outs], "rnea_fd", layout, B, str(tmp_path / d), budget, "_rank1")
+    tau, qdd = (np.load(tmp_path / "s1" / f"{k}_rank1.npy") for k in ("tau", "qdd"))
+    assert tau.dtype == np.float32 and tau.shape == qdd.shape == (n, 100)
+    assert tau.nbytes + qdd.nbytes <= budget
+    cols = tau[0].astype(np.int64)  # row 0 of `want[0]` is the column index itself
+    assert np.all(np.diff(cols) > 0) and cols[0] >= 0 and cols[-1] < B
+    np.testing.assert_array_equal(tau, want[0][:, cols].astype(np.float32))
+    np.testing.assert_array_equal(qdd, want[1][:, cols].astype(np.float32))
+    np.testing.assert_array_equal(tau, np.load(tmp_path / "s2" / "tau_rank1.npy"))
 
 
 def test_compact_line_of_a_full_driver_line():

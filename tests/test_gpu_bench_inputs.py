@@ -44,3 +44,42 @@ def test_rollout_launcher_resets_state(dtype, B):
     ro(0, None)
     torch.cuda.synchronize()
     assert torch.equal(torch.stack(ro.keep[:2]), ro.keep[3])
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run (no --full: no CPU baseline, no secondary
+    lines) on a ragged batch: DIR/tau.npy and DIR/qdd.npy are [n, B] float64 arrays, bit for bit
+    what the timed entry point (multibody_rnea_fd_batch_tiled_f64) gives on the input set of the
+    last timed step, that set drawn again here from its seed."""
+    import sys
+
+    import numpy as np
+
+    sys.path[:0] = [REPO, PKG]
+    from conftest import run_bench
+    from rigidbody_amd import chains, ffi
+    from rigidbody_amd import dist as rdist
+
+    B, steps = 1000, 3
+    out = tmp_path / "out"
+    compact, line = run_bench(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--kernel", "rnea_fd",
+                               "--batch", str(B), "--spinup-ms", "0", "--rotate-gib", "0.001",
+                               "--dump-outputs", str(out)])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and compact["ms_per_step"] == line["ms_per_step"]
+    assert "cpu_baseline" not in line and "secondary" not in line
+    assert line["dumped_outputs"]["arrays"] == {"tau": [7, B], "qdd": [7, B]}
+    ns = line["config"]["input_sets"]
+    assert ns > steps  # the last timed step ran on a set of its own, not on set 0
+    mb = ffi.Multibody.new()
+    mb.upload()
+    lim = mb.limits()
+    seed = rdist.rank_seed(chains.SEED, 0) + 1000 * ((steps - 1) % ns)
+    x = [ffi.to_tiled(ffi.fill_uniform(torch.empty((7, B), dtype=torch.float64, device="cuda"),
+                                       *chains.input_ranges(lim, kind), seed + k))
+         for k, kind in enumerate(("q", "qd", "qdd", "tau"))]
+    want = [ffi.from_tiled(t, B).cpu().numpy() for t in mb.rnea_fd_batch_tiled(*x, B)]
+    for name, w in zip(("tau", "qdd"), want):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == (7, B)
+        assert np.isfinite(got).all()
+        np.testing.assert_array_equal(got, w)

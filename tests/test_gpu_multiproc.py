@@ -137,7 +137,7 @@ def test_bench_two_ranks_strong_rnea_fd():
 
 
 def test_bench_two_ranks_weak_with_strong_split():
-    """The driver's N > 1 line shape (weak headline, --steps 20): the strong split beside it
+    """The N > 1 line shape of a --full run (weak headline, --steps 20): the strong split beside it
     times its own launch budget (>= SIDE_MIN_LAUNCHES on every rank), and both carry per-rank
     device / wall times."""
     import bench
@@ -145,7 +145,7 @@ def test_bench_two_ranks_weak_with_strong_split():
     e = dict(os.environ, RB_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         e.pop(k, None)
-    compact, line = run_bench(["--gpus", "2", "--batch", str(1 << 18), "--steps", "20", "--warmup", "5",
+    compact, line = run_bench(["--gpus", "2", "--batch", str(1 << 18), "--steps", "20", "--warmup", "5", "--full",
                                "--no-secondary", "--no-cpu-baseline", "--spinup-ms", "50", "--rotate-gib", "0.5"], e)
     assert set(compact["secondary"]) >= {"strong_split", "strong_split_rnea_fd"}
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["steps"] == 20
