@@ -16,6 +16,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <sstream>
@@ -85,7 +86,7 @@ struct Multibody {
     // model-specialised hipRTC kernels, keyed by (device, kind, dtype, trig, tuning tag, form)
     mutable std::map<std::string, rbamd::JitKernel> jit;
     mutable std::map<std::string, int> jit_device;
-    // per-launch fast path of jit_get: [device][kind][f64][fast trig][requested pack][tail] ->
+    // per-launch fast path of jit_get: [device][kind][f64][fast trig][pack][tail, nt] of the variant ->
     // the kernel resolved under one tuning generation, published as ONE pointer to a record
     // {generation, kernel}.  There is one record per (slot, kernel) pair, so the records are
     // bounded by slots x kernels however often the tuning changes: a record's kernel never
@@ -143,53 +144,42 @@ int device_consts(const Multibody *mb, const T **out) {
     }
     std::lock_guard<std::mutex> lk(mb->mu);
     DeviceConsts &dc = mb->dev[d];
+    T **block;
+    const std::vector<T> *host;
     if constexpr (sizeof(T) == 4) {
-        if (!dc.f32) {
-            void *p = nullptr;
-            size_t bytes = mb->pk32.size() * sizeof(float);
-            if ((e = hipMalloc(&p, bytes)) != hipSuccess) return hip_err(e, "hipMalloc(model)");
-            if ((e = hipMemcpy(p, mb->pk32.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-                (void)hipFree(p);
-                return hip_err(e, "hipMemcpy(model)");
-            }
-            dc.f32 = static_cast<float *>(p);
-        }
-        *out = reinterpret_cast<const T *>(dc.f32);
-        if (fastp) fastp->store(dc.f32, std::memory_order_release);
+        block = &dc.f32;
+        host = &mb->pk32;
     } else {
-        if (!dc.f64) {
-            void *p = nullptr;
-            size_t bytes = mb->pk64.size() * sizeof(double);
-            if ((e = hipMalloc(&p, bytes)) != hipSuccess) return hip_err(e, "hipMalloc(model)");
-            if ((e = hipMemcpy(p, mb->pk64.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-                (void)hipFree(p);
-                return hip_err(e, "hipMemcpy(model)");
-            }
-            dc.f64 = static_cast<double *>(p);
-        }
-        *out = reinterpret_cast<const T *>(dc.f64);
-        if (fastp) fastp->store(dc.f64, std::memory_order_release);
+        block = &dc.f64;
+        host = &mb->pk64;
     }
+    if (!*block) {
+        void *p = nullptr;
+        size_t bytes = host->size() * sizeof(T);
+        if ((e = hipMalloc(&p, bytes)) != hipSuccess) return hip_err(e, "hipMalloc(model)");
+        if ((e = hipMemcpy(p, host->data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+            (void)hipFree(p);
+            return hip_err(e, "hipMemcpy(model)");
+        }
+        *block = static_cast<T *>(p);
+    }
+    *out = *block;
+    if (fastp) fastp->store(*block, std::memory_order_release);
     return RB_OK;
 }
 
-// The hipRTC kernel of `kind` for this model on the current device, or nullptr (the
-// precompiled generic kernel then runs).
-// pack: configurations per lane, 0 = the jit_pack policy (jit.cpp).
-// tail: percent of a sequential-pair RNEA launch run one per lane (jit_seq_tail); other kinds 0.
-const rbamd::JitKernel *jit_get(const Multibody *mb, rbamd::JitKind kind, bool f64, bool fast, int pack = 0,
-                                int tail = 0, int nt = -1) {
+// The hipRTC kernel of variant `v` (jit.hpp jit_resolve) for this model on the current device,
+// or nullptr (the precompiled generic kernel then runs).
+const rbamd::JitKernel *jit_get(const Multibody *mb, const rbamd::JitVariant &v) {
     if (!rbamd::jit_enabled()) return nullptr;
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess) return nullptr;
-    const bool fst = fast && !f64;
     std::atomic<const Multibody::JitPub *> *slot = nullptr;
-    if (d >= 0 && d < 16 && (int)kind >= 0 && (int)kind < rbamd::kJitKinds && pack >= 0 && pack < 6) {
-        slot = &mb->jit_fast[d][(int)kind][f64 ? 1 : 0][fst ? 1 : 0][pack][(tail > 0 ? 1 : 0) | (nt >= 0 ? 2 : 0)];
+    if (d >= 0 && d < 16 && (int)v.kind >= 0 && (int)v.kind < rbamd::kJitKinds && v.pack >= 0 && v.pack < 6) {
+        slot = &mb->jit_fast[d][(int)v.kind][v.f64 ? 1 : 0][v.fast ? 1 : 0][v.pack][(v.tail > 0 ? 1 : 0) | (v.nt >= 0 ? 2 : 0)];
         if (const Multibody::JitPub *p = slot->load(std::memory_order_acquire))
             if (p->gen.load(std::memory_order_acquire) == rbamd::tuning_generation()) return p->jk;
     }
-    const int pack_req = pack;
     std::lock_guard<std::mutex> lk(mb->mu);
     // The tuning generation is a sequence count (tuning.cpp): odd while rb_set_tuning writes,
     // bumped again after.  The key and the kernel source both read the tuning knobs, so they are
@@ -197,14 +187,10 @@ const rbamd::JitKernel *jit_get(const Multibody *mb, rbamd::JitKind kind, bool f
     // kernel built from a mix of two tunings is never stored under either key).
     for (;;) {
         const unsigned gen = rbamd::tuning_generation_stable();
-        int pk = pack_req > 0 ? pack_req : rbamd::jit_model_pack(mb->model, kind, f64, 0);
-        const int tl = (kind == rbamd::JitKind::Rnea && pk == 3) ? tail : 0;
-        const std::string key = std::to_string(d) + ":k" + std::to_string((int)kind) + (f64 ? ":f64" : ":f32") +
-                                (fst ? ":fast" : ":precise") + rbamd::jit_tag(kind, f64, mb->model.n) + ":q" +
-                                std::to_string(pk) + ":st" + std::to_string(tl) + ":n" + std::to_string(nt);
+        const std::string key = std::to_string(d) + rbamd::jit_key(mb->model, v);
         auto it = mb->jit.find(key);
         if (it == mb->jit.end()) {
-            rbamd::JitKernel built = rbamd::jit_build(mb->model, kind, f64, fst, pk, tl, nt);
+            rbamd::JitKernel built = rbamd::jit_build(mb->model, v);
             if (rbamd::tuning_generation() != gen) {  // the tuning moved under the build
                 if (built.module) (void)hipModuleUnload(built.module);
                 continue;
@@ -227,42 +213,6 @@ const rbamd::JitKernel *jit_get(const Multibody *mb, rbamd::JitKind kind, bool f
     }
 }
 
-// Smallest batch for which the auto policy takes the sequential-pair fp64 RNEA (jit_pack 3):
-// it halves the waves, so below two resident rounds of the one-per-lane kernel (4 waves/SIMD x
-// 1024 SIMDs x 64 lanes x 2) the one-per-lane kernel keeps more of the chip busy.
-constexpr uint32_t kSeqMinBatch = 1u << 19;
-
-// The hipRTC kernel variant a launch takes: configurations per lane (0 = the jit_pack policy),
-// the sequential pair's one-per-lane tail, the non-temporal override and the fp32 trig form.
-// The launch paths and the inspection entry points (multibody_jit_source_ex) share it.
-struct JitShape {
-    int pack = 0, tail = 0, nt = -1;
-    bool fast = false;
-};
-JitShape jit_shape(const Multibody *mb, rbamd::JitKind kind, bool f64, uint32_t B, bool tiled);
-
-const rbamd::JitKernel *jit_shaped(const Multibody *mb, rbamd::JitKind kind, bool f64, uint32_t B, bool tiled) {
-    const JitShape sh = jit_shape(mb, kind, f64, B, tiled);
-    return jit_get(mb, kind, f64, sh.fast, sh.pack, sh.tail, sh.nt);
-}
-
-JitShape rnea_shape(const Multibody *mb, bool f64, uint32_t B, bool tiled) {
-    // fp32 chains up to 8 links on the tiled layout at large batches: the sequential pair too
-    // (FR3 2^20 22.0-22.1 vs 22.3-24.0 us on two boxes, profiles/r04/ab/ab_r32_seq*.log), with
-    // ordinary (temporal) loads and stores (tuning.hpp rnea_nt; the 30-link chain and the 14-DOF
-    // tree keep nt = 3)
-    const bool big32 = !f64 && tiled && B >= kSeqMinBatch && mb->model.n <= 8;
-    JitShape sh;
-    sh.pack = rbamd::tuning().pack >= 0 ? 0 : big32 ? 3 : B < kSeqMinBatch ? 1 : 0;
-    sh.nt = (big32 && rbamd::tuning().rnea_nt < 0) ? 0 : -1;
-    sh.tail = rbamd::jit_seq_tail(tiled);
-    return sh;
-}
-
-const rbamd::JitKernel *jit_rnea(const Multibody *mb, bool f64, uint32_t B, bool tiled) {
-    return jit_shaped(mb, rbamd::JitKind::Rnea, f64, B, tiled);
-}
-
 // A tree / prismatic model has no precompiled kernel: without its hipRTC kernel the launch
 // is refused (hipErrorNotSupported, reported as RB_ERR_UNSUPPORTED with the reason).
 hipError_t no_generic(const Multibody *mb) {
@@ -278,82 +228,42 @@ hipError_t no_generic(const Multibody *mb) {
     return hipErrorNotSupported;
 }
 
-// Smallest batch for which the auto policy takes the paired-lane kernel: one resident round
-// of it (2 blocks of 512 configurations per CU x 256 CUs) -- 2^18.
-constexpr uint32_t kPackMinBatch = 1u << 18;
-// fp32 mass-matrix forward dynamics at small batches: one wave per SIMD at most, so the launch
-// time follows each wave's instruction stream; the wave splits (fdh_body.hip.hpp) halve it.
-// Up to 2^17 configurations the one-per-lane split (pack 5: B/32 waves, its roles alternating
-// over the SIMDs), above it the packed pair; the packed split (pack 4: B/64 waves) is the
-// rollout's, with the same bound.  FR3, HIP graph (profiles/r06/mix/): 32768 3.53 us (pack 5)
-// / 3.99 (4); 65536 4.15 (5) / 4.24 (4); 131072 5.45 (5) / 5.50 (4).
-constexpr uint32_t kSplitMaxBatch = 1u << 17;
-
-// The forward-dynamics kernel a launch of B configurations takes (auto policy when the
-// tuning `pack` is unset).
-int fd_pack(const Multibody *mb, bool f64, uint32_t B) {
-    int pack = 0;
-    if (rbamd::tuning().pack < 0) {
-        if (!f64 && rbamd::jit_fd_form(mb->model) == 2 && mb->model.n <= 8 &&
-            mb->model.serial_revolute())  // splits: serial chains, measured on FR3
-            pack = B <= kSplitMaxBatch ? 5 : 0;
-        else  // paired lanes halve the grid: below kPackMinBatch one per lane fills more CUs
-            pack = B < kPackMinBatch ? 1 : 0;
-    }
-    return pack;
+// Serial revolute chains take the precompiled kinematics kernels only when the (experimental)
+// tuning `kin_jit` is 0.
+bool kin_precompiled(const Multibody *mb) {
+    return mb->model.serial_revolute() && rbamd::tuning().kin_jit == 0;
 }
 
-const rbamd::JitKernel *jit_fd(const Multibody *mb, bool f64, uint32_t B) {
-    return jit_shaped(mb, rbamd::JitKind::Fd, f64, B, false);
-}
-
-// The rollout kernel a launch of B configurations takes: fp32 mass-matrix rollouts up to 2^17
-// configurations split every step over a pair of packed waves (aba_body.hip.hpp
-// rollout_split_block2), as jit_fd's small-batch forward dynamics.  FR3, K = 16, HIP graph:
-// 16384 43.3 vs 62.7 us (pair), 65536 43.6 vs 63.5, 131072 58.9 vs 63.7; 262144 101.5 vs 93.2
-// (profiles/r03/rollout_split/).
-int rollout_pack(const Multibody *mb, bool f64, uint32_t B) {
-    return (rbamd::tuning().pack < 0 && !f64 && B <= kSplitMaxBatch &&
-            rbamd::jit_fd_form(mb->model, rbamd::JitKind::Rollout) == 2 &&
-            !(rbamd::tuning().jit_variant & 256)) ? 4 : 0;
-}
-
-const rbamd::JitKernel *jit_rollout(const Multibody *mb, bool f64, uint32_t B) {
-    return jit_shaped(mb, rbamd::JitKind::Rollout, f64, B, false);
-}
-
-int idfd_pack(bool f64, uint32_t B);
-
-JitShape jit_shape(const Multibody *mb, rbamd::JitKind kind, bool f64, uint32_t B, bool tiled) {
-    JitShape sh;
-    switch (kind) {
-        case rbamd::JitKind::Rnea: sh = rnea_shape(mb, f64, B, tiled); break;
-        case rbamd::JitKind::Fd: sh.pack = fd_pack(mb, f64, B); break;
-        case rbamd::JitKind::Rollout: sh.pack = rollout_pack(mb, f64, B); break;
-        case rbamd::JitKind::RneaFd: sh.pack = idfd_pack(f64, B); break;
-        default: break;
-    }
-    // CRBA evaluates its angles with the precise fp32 sincos; every other kind with the fast one
-    // unless RB_FAST_TRIG=0 (fp64 always its own)
-    sh.fast = kind != rbamd::JitKind::Crba && fast_trig() && !f64;
-    return sh;
-}
-
-unsigned jit_grid(const rbamd::JitKernel *jk, uint32_t B) {
-    if (jk->pack == 3 && jk->seq_tail > 0) {  // pairs, then a one-per-lane tail (jit.cpp)
-        const unsigned T = (unsigned)(((uint64_t)B + 255u) / 256u);
-        const unsigned S = (unsigned)(((uint64_t)T * (unsigned)jk->seq_tail) / 100u);
-        const unsigned P = (T - S) & ~1u;
-        return P / 2u + (T - P);
-    }
-    // pack 2 / 3: two configurations per lane; pack 5: the one-per-lane wave split, 128 per block
-    // (pack 4, the packed split, covers 256 per block like one per lane)
-    const unsigned per_block = jk->pack == 5 ? 128u : 256u * ((jk->pack == 2 || jk->pack == 3) ? 2u : 1u);
-    return (unsigned)(((uint64_t)B + per_block - 1) / per_block);
+// The hipRTC kernel a launch of B configurations of `kind` takes, or nullptr for the generic
+// path.  The launchers and the inspection entry points (multibody_kernel_path_ex / _form_ex)
+// resolve through this one; which variant it is, is jit_resolve's business (jit.cpp), CRBA's
+// always-precise trig included.
+const rbamd::JitKernel *kernel_for(const Multibody *mb, rbamd::JitKind kind, bool f64, uint32_t B, bool tiled) {
+    // fwd_kin / jac: the hipRTC kernels (tree_body.hip.hpp fwd_kin_tree / jac_tree, the model's
+    // topology and constants compiled in) for every model; serial revolute chains fall back to the
+    // precompiled kernels (kinematics.hip) when hipRTC is off or failed.  FR3 2^20: fwd_kin fp64
+    // 18.2 vs 26.4 us precompiled, fp32 9.6 vs 11.3; the Jacobian is store-bound, equal (89.2 vs
+    // 89.5 / 41.4 vs 41.3 us; profiles/r04/ab/ab_fk*.log, ab_jac*.log).
+    if ((kind == rbamd::JitKind::FwdKin || kind == rbamd::JitKind::Jac) && kin_precompiled(mb)) return nullptr;
+    // the fused inverse + forward dynamics exists for serial chains on the mass-matrix form only
+    // (jit_fd_form is 1 for this kind on every model that is not a serial revolute chain)
+    if (kind == rbamd::JitKind::RneaFd && rbamd::jit_fd_form(mb->model, rbamd::JitKind::RneaFd) != 2) return nullptr;
+    return jit_get(mb, rbamd::jit_resolve(mb->model, kind, f64, B, tiled, fast_trig()));
 }
 
 hipError_t jit_launch(const rbamd::JitKernel *jk, uint32_t B, void **args, hipStream_t s) {
-    return hipModuleLaunchKernel(jk->function, jit_grid(jk, B), 1, 1, jk->block, 1, 1, 0, s, args, nullptr);
+    return hipModuleLaunchKernel(jk->function, rbamd::jit_grid(*jk, B), 1, 1, jk->block, 1, 1, 0, s, args, nullptr);
+}
+
+// Strides (elements) the JIT lane kernels take for arrays of rows_in / rows_out rows per
+// configuration: the row stride, and the stride from one 256-configuration block to the next --
+// 256 for SoA rows of length ld, rows * 256 for the tiled layout (kernels.hpp).
+struct TileStrides {
+    int64_t lda, bs_in, bs_out;
+};
+TileStrides tile_strides(bool tiled, int64_t ld, int64_t rows_in, int64_t rows_out) {
+    if (!tiled) return {ld, 256, 256};
+    return {256, rows_in * 256, rows_out * 256};
 }
 
 // tiled: the [ceil(B/256)][n][256] layout (kernels.hpp); the JIT lane kernels and the
@@ -363,9 +273,9 @@ template <typename T>
 hipError_t launch_rnea_any(const Multibody *mb, const T *mdl, const T *q, const T *qd, const T *qdd, T *tau,
                            uint32_t B, int64_t ld, hipStream_t s, bool tiled = false) {
     if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = jit_rnea(mb, sizeof(T) == 8, B, tiled)) {
-        const int64_t lda = tiled ? 256 : ld, bs = tiled ? (int64_t)mb->model.n * 256 : 256;
-        void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&tau, (void *)&B, (void *)&lda, (void *)&bs};
+    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Rnea, sizeof(T) == 8, B, tiled)) {
+        TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
+        void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&tau, (void *)&B, (void *)&st.lda, (void *)&st.bs_in};
         return jit_launch(jk, B, args, s);
     }
     if (!mb->model.serial_revolute()) return no_generic(mb);
@@ -376,9 +286,9 @@ template <typename T>
 hipError_t launch_fd_any(const Multibody *mb, const T *mdl, const T *q, const T *qd, const T *tau, T *qdd,
                          uint32_t B, int64_t ld, hipStream_t s, bool tiled = false) {
     if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = jit_fd(mb, sizeof(T) == 8, B)) {
-        const int64_t lda = tiled ? 256 : ld, bs = tiled ? (int64_t)mb->model.n * 256 : 256;
-        void *args[] = {(void *)&q, (void *)&qd, (void *)&tau, (void *)&qdd, (void *)&B, (void *)&lda, (void *)&bs};
+    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Fd, sizeof(T) == 8, B, tiled)) {
+        TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
+        void *args[] = {(void *)&q, (void *)&qd, (void *)&tau, (void *)&qdd, (void *)&B, (void *)&st.lda, (void *)&st.bs_in};
         return jit_launch(jk, B, args, s);
     }
     if (!mb->model.serial_revolute()) return no_generic(mb);
@@ -389,33 +299,14 @@ hipError_t launch_fd_any(const Multibody *mb, const T *mdl, const T *q, const T 
 // (fdh_body.hip.hpp idfd_lane) for models on the mass-matrix forward dynamics; otherwise -- the
 // ABA models (trees, chains over 12 links), hipRTC off or failed -- the RNEA launch then the
 // forward-dynamics launch, the same results.
-// The fused pair's kernel form for B configurations (auto policy when the tuning `pack` is
-// unset): the wave split (pack 5, idfd_split_block1) for fp32 up to 2^16 configurations, one
-// per lane otherwise.  FR3, HIP graph, tiled (profiles/r06/split/): fp32 65536 4.82 vs 5.24 us,
-// 131072 6.79 vs 6.49; fp64 65536 6.64 vs 6.70, 131072 11.55 vs 10.67, 262144 22.06 vs 20.59 --
-// as for the forward dynamics alone (fp64 FD split 10.16 vs 8.62 us at 2^17): the SIMDs already
-// hold 2 waves of the one-per-lane kernel there, and the split repeats the loads and sincos.
-// With the split's roles alternating over the SIMDs (round 6, profiles/r06/mix/): fp32 65536
-// 4.75 us, 131072 6.53 vs 6.46 one per lane -- the bound stays.
-constexpr uint32_t kIdfdSplitMaxBatch32 = 1u << 16;
-int idfd_pack(bool f64, uint32_t B) {
-    if (rbamd::tuning().pack >= 0) return 0;
-    return (!f64 && B <= kIdfdSplitMaxBatch32) ? 5 : 1;
-}
-
-const rbamd::JitKernel *jit_idfd(const Multibody *mb, bool f64, uint32_t B) {
-    if (!mb->model.serial_revolute() || rbamd::jit_fd_form(mb->model, rbamd::JitKind::RneaFd) != 2) return nullptr;
-    return jit_shaped(mb, rbamd::JitKind::RneaFd, f64, B, false);
-}
-
 template <typename T>
 hipError_t launch_idfd_any(const Multibody *mb, const T *mdl, const T *q, const T *qd, const T *qdd, const T *tau_in,
                            T *tau, T *qdd_out, uint32_t B, int64_t ld, hipStream_t s, bool tiled = false) {
     if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = jit_idfd(mb, sizeof(T) == 8, B)) {
-        const int64_t lda = tiled ? 256 : ld, bs = tiled ? (int64_t)mb->model.n * 256 : 256;
+    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::RneaFd, sizeof(T) == 8, B, tiled)) {
+        TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
         void *args[] = {(void *)&q,   (void *)&qd, (void *)&qdd,  (void *)&tau_in, (void *)&tau,
-                        (void *)&qdd_out, (void *)&B, (void *)&lda, (void *)&bs};
+                        (void *)&qdd_out, (void *)&B, (void *)&st.lda, (void *)&st.bs_in};
         return jit_launch(jk, B, args, s);
     }
     hipError_t e = launch_rnea_any<T>(mb, mdl, q, qd, qdd, tau, B, ld, s, tiled);
@@ -427,7 +318,7 @@ template <typename T>
 hipError_t launch_rollout_any(const Multibody *mb, const T *mdl, T *q, T *qd, const T *tau_seq, T dt, int K, T *traj,
                               uint32_t B, int64_t ld, hipStream_t s) {
     if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = jit_rollout(mb, sizeof(T) == 8, B)) {
+    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Rollout, sizeof(T) == 8, B, false)) {
         void *args[] = {(void *)&q, (void *)&qd, (void *)&tau_seq, (void *)&dt, (void *)&K, (void *)&traj,
                         (void *)&B, (void *)&ld};
         return jit_launch(jk, B, args, s);
@@ -440,30 +331,14 @@ template <typename T>
 hipError_t launch_crba_any(const Multibody *mb, const T *mdl, const T *q, T *H, uint32_t B, int64_t ld,
                            hipStream_t s, bool tiled = false) {
     if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = jit_get(mb, rbamd::JitKind::Crba, sizeof(T) == 8, false)) {
-        const int64_t n = mb->model.n, lda = tiled ? 256 : ld, bs_in = tiled ? n * 256 : 256,
-                      bs_out = tiled ? n * n * 256 : 256;
-        void *args[] = {(void *)&q, (void *)&H, (void *)&B, (void *)&lda, (void *)&bs_in, (void *)&bs_out};
+    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Crba, sizeof(T) == 8, B, tiled)) {
+        const int64_t n = mb->model.n;
+        TileStrides st = tile_strides(tiled, ld, n, n * n);
+        void *args[] = {(void *)&q, (void *)&H, (void *)&B, (void *)&st.lda, (void *)&st.bs_in, (void *)&st.bs_out};
         return jit_launch(jk, B, args, s);
     }
     if (!mb->model.serial_revolute()) return no_generic(mb);
     return rbamd::launch_crba<T>(mb->model.n, mdl, q, H, B, ld, s, tiled);
-}
-
-// fwd_kin / jac: the hipRTC kernels (tree_body.hip.hpp fwd_kin_tree / jac_tree, the model's
-// topology and constants compiled in) for every model; serial revolute chains fall back to the
-// precompiled kernels (kinematics.hip) when hipRTC is off or failed.  FR3 2^20: fwd_kin fp64
-// 18.2 vs 26.4 us precompiled, fp32 9.6 vs 11.3; the Jacobian is store-bound, equal (89.2 vs
-// 89.5 / 41.4 vs 41.3 us; profiles/r04/ab/ab_fk*.log, ab_jac*.log).  The launchers and
-// multibody_kernel_path_ex resolve through this one.
-const rbamd::JitKernel *jit_kin(const Multibody *mb, bool jac, bool f64) {
-    return jit_get(mb, jac ? rbamd::JitKind::Jac : rbamd::JitKind::FwdKin, f64, !f64 && fast_trig());
-}
-
-// Serial revolute chains take the precompiled kinematics kernels only when the (experimental)
-// tuning `kin_jit` is 0.
-bool kin_precompiled(const Multibody *mb) {
-    return mb->model.serial_revolute() && rbamd::tuning().kin_jit == 0;
 }
 
 template <typename T>
@@ -471,14 +346,15 @@ hipError_t launch_kin_any(const Multibody *mb, bool jac, const T *mdl, const T *
                           hipStream_t s, bool tiled = false) {
     if (B == 0) return hipSuccess;
     const bool fast = sizeof(T) == 4 && fast_trig();
-    const rbamd::JitKernel *jk = kin_precompiled(mb) ? nullptr : jit_kin(mb, jac, sizeof(T) == 8);
+    const rbamd::JitKernel *jk =
+        kernel_for(mb, jac ? rbamd::JitKind::Jac : rbamd::JitKind::FwdKin, sizeof(T) == 8, B, tiled);
     if (!jk && mb->model.serial_revolute())
         return jac ? rbamd::launch_jac<T>(mb->model.n, mdl, q, out, B, ld, s, fast, tiled)
                    : rbamd::launch_fwd_kin<T>(mb->model.n, mdl, q, out, B, ld, s, fast, tiled);
     if (!jk) return no_generic(mb);
-    const int64_t n = mb->model.n, lda = tiled ? 256 : ld, bs_in = tiled ? n * 256 : 256,
-                  bs_out = tiled ? (jac ? 6 * n : 3) * 256 : 256;
-    void *args[] = {(void *)&q, (void *)&out, (void *)&B, (void *)&lda, (void *)&bs_in, (void *)&bs_out};
+    const int64_t n = mb->model.n;
+    TileStrides st = tile_strides(tiled, ld, n, jac ? 6 * n : 3);
+    void *args[] = {(void *)&q, (void *)&out, (void *)&B, (void *)&st.lda, (void *)&st.bs_in, (void *)&st.bs_out};
     return jit_launch(jk, B, args, s);
 }
 
@@ -572,6 +448,26 @@ double *single_query(const Multibody *mb, const double *const *inputs, int nin, 
     return res;
 }
 
+// One single-configuration query of the reference ABI: on the host where that is allowed
+// (`host(out)`, single_host), else one GPU launch (`gpu(mdl, dev_in, dev_out, stream)`,
+// single_query); `where` labels a failed launch.
+template <typename Host, typename Gpu>
+double *single_config(const Multibody *mb, std::initializer_list<const double *> inputs, size_t nout, const char *where,
+                      Host host, Gpu gpu) {
+    const double *const *in = inputs.begin();
+    const int nin = (int)inputs.size();
+    bool used = false;
+    double *r = single_host(mb, in, nin, nout, &used, host);
+    if (used) return r;
+    return single_query(mb, in, nin, nout, [&](double *din, double *dout, hipStream_t s) {
+        const double *mdl = nullptr;
+        int rc = device_consts<double>(mb, &mdl);
+        if (rc) return rc;
+        hipError_t e = gpu(mdl, din, dout, s);
+        return e == hipSuccess ? RB_OK : hip_err(e, where);
+    });
+}
+
 template <typename T, typename L>
 int chunked(int64_t batch, L &&one) {
     for (int64_t b0 = 0; b0 < batch; b0 += kChunk) {
@@ -582,110 +478,104 @@ int chunked(int64_t batch, L &&one) {
     return RB_OK;
 }
 
-template <typename T>
-int rnea_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *tau, int64_t batch,
-               int64_t ld, void *stream, bool tiled = false) {
+int no_null(std::initializer_list<const void *> arrays) {
+    for (const void *p : arrays)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    return RB_OK;
+}
+
+// The spine of every batched entry point.  Argument errors are reported in this order: handle,
+// batch, ld (check_batch), then the entry point's own arrays (`args_ok`: its NULL check, and
+// whatever else it refuses), then the device.  `launch(mdl, b0, nb)` enqueues configurations
+// [b0, b0 + nb) -- at most kChunk of them, b0 a multiple of 256; `where` labels its failure.
+template <typename T, typename Check, typename Launch>
+int batch_call(const Multibody *mb, int64_t batch, int64_t ld, bool tiled, Check args_ok, const char *where,
+               Launch launch) {
     int rc = check_batch(mb, batch, tiled ? batch : ld);
     if (rc) return rc;
     if (batch == 0) return RB_OK;
-    if (!q || !qd || !qdd || !tau) return set_err(RB_ERR_NULL, "NULL array");
+    if ((rc = args_ok())) return rc;
     const T *mdl = nullptr;
     if ((rc = device_consts<T>(mb, &mdl))) return rc;
-    const int64_t per = tiled ? mb->model.n : 1;  // element offset of configuration b0 (b0 % 256 == 0)
     return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        const int64_t o = b0 * per;
-        hipError_t e = launch_rnea_any<T>(mb, mdl, q + o, qd + o, qdd + o, tau + o, nb, ld, (hipStream_t)stream, tiled);
-        return e == hipSuccess ? RB_OK : hip_err(e, "rnea launch");
+        hipError_t e = launch(mdl, b0, nb);
+        return e == hipSuccess ? RB_OK : hip_err(e, where);
+    });
+}
+
+template <typename T>
+int rnea_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *tau, int64_t batch,
+               int64_t ld, void *stream, bool tiled = false) {
+    return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, qd, qdd, tau}); }, "rnea launch",
+                         [&](const T *mdl, int64_t b0, uint32_t nb) {
+        const int64_t o = b0 * (tiled ? mb->model.n : 1);  // element offset of configuration b0 (b0 % 256 == 0)
+        return launch_rnea_any<T>(mb, mdl, q + o, qd + o, qdd + o, tau + o, nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
 template <typename T>
 int fd_batch(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, int64_t batch,
              int64_t ld, void *stream, bool tiled = false) {
-    int rc = check_batch(mb, batch, tiled ? batch : ld);
-    if (rc) return rc;
-    if (batch == 0) return RB_OK;
-    if (!q || !qd || !tau || !qdd) return set_err(RB_ERR_NULL, "NULL array");
-    const T *mdl = nullptr;
-    if ((rc = device_consts<T>(mb, &mdl))) return rc;
-    const int64_t per = tiled ? mb->model.n : 1;
-    return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        const int64_t o = b0 * per;
-        hipError_t e = launch_fd_any<T>(mb, mdl, q + o, qd + o, tau + o, qdd + o, nb, ld, (hipStream_t)stream, tiled);
-        return e == hipSuccess ? RB_OK : hip_err(e, "aba launch");
+    return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, qd, tau, qdd}); }, "aba launch",
+                         [&](const T *mdl, int64_t b0, uint32_t nb) {
+        const int64_t o = b0 * (tiled ? mb->model.n : 1);
+        return launch_fd_any<T>(mb, mdl, q + o, qd + o, tau + o, qdd + o, nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
 template <typename T>
 int idfd_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, const T *tau_in, T *tau, T *qdd_out,
                int64_t batch, int64_t ld, void *stream, bool tiled = false) {
-    int rc = check_batch(mb, batch, tiled ? batch : ld);
-    if (rc) return rc;
-    if (batch == 0) return RB_OK;
-    if (!q || !qd || !qdd || !tau_in || !tau || !qdd_out) return set_err(RB_ERR_NULL, "NULL array");
-    // outputs must not overlap the inputs (the kernel reads tau_in after storing tau); the exact
-    // aliases a caller is likely to pass -- tau_in as tau, qdd as qdd_out -- are refused here
-    for (const T *o : {(const T *)tau, (const T *)qdd_out})
-        for (const T *i : {q, qd, qdd, tau_in})
-            if (o == i) return set_err(RB_ERR_ARG, "rnea_fd: an output array is also an input (no in-place form)");
-    if (tau == qdd_out) return set_err(RB_ERR_ARG, "rnea_fd: tau and qdd_out are the same array");
-    const T *mdl = nullptr;
-    if ((rc = device_consts<T>(mb, &mdl))) return rc;
-    const int64_t per = tiled ? mb->model.n : 1;
-    return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        const int64_t o = b0 * per;
-        hipError_t e = launch_idfd_any<T>(mb, mdl, q + o, qd + o, qdd + o, tau_in + o, tau + o, qdd_out + o, nb, ld,
-                                          (hipStream_t)stream, tiled);
-        return e == hipSuccess ? RB_OK : hip_err(e, "rnea_fd launch");
+    auto args_ok = [&] {
+        if (int rc = no_null({q, qd, qdd, tau_in, tau, qdd_out})) return rc;
+        // outputs must not overlap the inputs (the kernel reads tau_in after storing tau); the exact
+        // aliases a caller is likely to pass -- tau_in as tau, qdd as qdd_out -- are refused here
+        for (const T *o : {(const T *)tau, (const T *)qdd_out})
+            for (const T *i : {q, qd, qdd, tau_in})
+                if (o == i) return set_err(RB_ERR_ARG, "rnea_fd: an output array is also an input (no in-place form)");
+        if (tau == qdd_out) return set_err(RB_ERR_ARG, "rnea_fd: tau and qdd_out are the same array");
+        return (int)RB_OK;
+    };
+    return batch_call<T>(mb, batch, ld, tiled, args_ok, "rnea_fd launch", [&](const T *mdl, int64_t b0, uint32_t nb) {
+        const int64_t o = b0 * (tiled ? mb->model.n : 1);
+        return launch_idfd_any<T>(mb, mdl, q + o, qd + o, qdd + o, tau_in + o, tau + o, qdd_out + o, nb, ld,
+                                  (hipStream_t)stream, tiled);
     });
 }
 
 template <typename T>
 int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt, int K, T *traj, int64_t batch,
                   int64_t ld, void *stream) {
+    // the step count is checked after handle / batch / ld and before the empty-batch return, so
+    // check_batch runs here and once more (cheap, same answer) inside batch_call
     int rc = check_batch(mb, batch, ld);
     if (rc) return rc;
     if (K < 0) return set_err(RB_ERR_ARG, "negative step count");
-    if (batch == 0 || K == 0) return RB_OK;
-    if (!q || !qd || !tau_seq) return set_err(RB_ERR_NULL, "NULL array");
-    const T *mdl = nullptr;
-    if ((rc = device_consts<T>(mb, &mdl))) return rc;
-    return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        hipError_t e = launch_rollout_any<T>(mb, mdl, q + b0, qd + b0, tau_seq + b0, (T)dt, K,
-                                             traj ? traj + b0 : nullptr, nb, ld, (hipStream_t)stream);
-        return e == hipSuccess ? RB_OK : hip_err(e, "rollout launch");
+    if (K == 0) return RB_OK;
+    return batch_call<T>(mb, batch, ld, false, [&] { return no_null({q, qd, tau_seq}); }, "rollout launch",
+                         [&](const T *mdl, int64_t b0, uint32_t nb) {
+        return launch_rollout_any<T>(mb, mdl, q + b0, qd + b0, tau_seq + b0, (T)dt, K, traj ? traj + b0 : nullptr, nb,
+                                     ld, (hipStream_t)stream);
     });
 }
 
 template <typename T>
 int crba_batch(const Multibody *mb, const T *q, T *H, int64_t batch, int64_t ld, void *stream, bool tiled = false) {
-    int rc = check_batch(mb, batch, tiled ? batch : ld);
-    if (rc) return rc;
-    if (batch == 0) return RB_OK;
-    if (!q || !H) return set_err(RB_ERR_NULL, "NULL array");
-    const T *mdl = nullptr;
-    if ((rc = device_consts<T>(mb, &mdl))) return rc;
-    // element offsets of configuration b0 (b0 % 256 == 0) in the input / output arrays
-    const int64_t n = mb->model.n, pin = tiled ? n : 1, pout = tiled ? n * n : 1;
-    return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        hipError_t e = launch_crba_any<T>(mb, mdl, q + b0 * pin, H + b0 * pout, nb, ld, (hipStream_t)stream, tiled);
-        return e == hipSuccess ? RB_OK : hip_err(e, "crba launch");
+    return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, H}); }, "crba launch",
+                         [&](const T *mdl, int64_t b0, uint32_t nb) {
+        // element offsets of configuration b0 (b0 % 256 == 0) in the input / output arrays
+        const int64_t n = mb->model.n, pin = tiled ? n : 1, pout = tiled ? n * n : 1;
+        return launch_crba_any<T>(mb, mdl, q + b0 * pin, H + b0 * pout, nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
 template <typename T>
 int kin_batch(const Multibody *mb, bool jac, const T *q, T *out, int64_t batch, int64_t ld, void *stream,
               bool tiled = false) {
-    int rc = check_batch(mb, batch, tiled ? batch : ld);
-    if (rc) return rc;
-    if (batch == 0) return RB_OK;
-    if (!q || !out) return set_err(RB_ERR_NULL, "NULL array");
-    const T *mdl = nullptr;
-    if ((rc = device_consts<T>(mb, &mdl))) return rc;
-    const int64_t n = mb->model.n, pin = tiled ? n : 1, pout = tiled ? (jac ? 6 * n : 3) : 1;
-    return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        hipError_t e = launch_kin_any<T>(mb, jac, mdl, q + b0 * pin, out + b0 * pout, nb, ld, (hipStream_t)stream, tiled);
-        return e == hipSuccess ? RB_OK : hip_err(e, jac ? "jac launch" : "fwd_kin launch");
+    return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, out}); }, jac ? "jac launch" : "fwd_kin launch",
+                         [&](const T *mdl, int64_t b0, uint32_t nb) {
+        const int64_t n = mb->model.n, pin = tiled ? n : 1, pout = tiled ? (jac ? 6 * n : 3) : 1;
+        return launch_kin_any<T>(mb, jac, mdl, q + b0 * pin, out + b0 * pout, nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
@@ -826,70 +716,39 @@ void multibody_free(Multibody *mb) {
 }
 
 double *multibody_rnea(const Multibody *mb, const double *q, const double *dq, const double *ddq) {
-    const double *in[3] = {q, dq, ddq};
     const size_t n = mb ? (size_t)mb->model.n : 0;
-    bool host = false;
-    double *r = single_host(mb, in, 3, n, &host, [&](double *o) {
-        return rbamd::host_rnea(mb->model, mb->pk64.data(), q, dq, ddq, o);
-    });
-    if (host) return r;
-    return single_query(mb, in, 3, n, [&](double *din, double *dout, hipStream_t s) {
-        const double *mdl = nullptr;
-        int rc = device_consts<double>(mb, &mdl);
-        if (rc) return rc;
-        hipError_t e = launch_rnea_any<double>(mb, mdl, din, din + n, din + 2 * n, dout, 1, 1, s);
-        return e == hipSuccess ? RB_OK : hip_err(e, "rnea launch");
-    });
+    return single_config(
+        mb, {q, dq, ddq}, n, "rnea launch",
+        [&](double *o) { return rbamd::host_rnea(mb->model, mb->pk64.data(), q, dq, ddq, o); },
+        [&](const double *mdl, double *din, double *dout, hipStream_t s) {
+            return launch_rnea_any<double>(mb, mdl, din, din + n, din + 2 * n, dout, 1, 1, s);
+        });
 }
 
 double *multibody_crba(const Multibody *mb, const double *q) {
-    const double *in[1] = {q};
     const size_t n = mb ? (size_t)mb->model.n : 0;
-    bool host = false;
-    double *r = single_host(mb, in, 1, n * n, &host, [&](double *o) {
-        return rbamd::host_crba(mb->model, mb->pk64.data(), q, o);
-    });
-    if (host) return r;
-    return single_query(mb, in, 1, n * n, [&](double *din, double *dout, hipStream_t s) {
-        const double *mdl = nullptr;
-        int rc = device_consts<double>(mb, &mdl);
-        if (rc) return rc;
-        hipError_t e = launch_crba_any<double>(mb, mdl, din, dout, 1, 1, s);
-        return e == hipSuccess ? RB_OK : hip_err(e, "crba launch");
-    });
+    return single_config(
+        mb, {q}, n * n, "crba launch", [&](double *o) { return rbamd::host_crba(mb->model, mb->pk64.data(), q, o); },
+        [&](const double *mdl, double *din, double *dout, hipStream_t s) {
+            return launch_crba_any<double>(mb, mdl, din, dout, 1, 1, s);
+        });
 }
 
 double *multibody_fwd_kin(const Multibody *mb, const double *q) {
-    const double *in[1] = {q};
-    bool host = false;
-    double *r = single_host(mb, in, 1, 3, &host, [&](double *o) {
-        return rbamd::host_fwd_kin(mb->model, mb->pk64.data(), q, o);
-    });
-    if (host) return r;
-    return single_query(mb, in, 1, 3, [&](double *din, double *dout, hipStream_t s) {
-        const double *mdl = nullptr;
-        int rc = device_consts<double>(mb, &mdl);
-        if (rc) return rc;
-        hipError_t e = launch_kin_any<double>(mb, false, mdl, din, dout, 1, 1, s);
-        return e == hipSuccess ? RB_OK : hip_err(e, "fwd_kin launch");
-    });
+    return single_config(
+        mb, {q}, 3, "fwd_kin launch", [&](double *o) { return rbamd::host_fwd_kin(mb->model, mb->pk64.data(), q, o); },
+        [&](const double *mdl, double *din, double *dout, hipStream_t s) {
+            return launch_kin_any<double>(mb, false, mdl, din, dout, 1, 1, s);
+        });
 }
 
 double *multibody_jac(const Multibody *mb, const double *q) {
-    const double *in[1] = {q};
     const size_t n = mb ? (size_t)mb->model.n : 0;
-    bool host = false;
-    double *r = single_host(mb, in, 1, 6 * n, &host, [&](double *o) {
-        return rbamd::host_jac(mb->model, mb->pk64.data(), q, o);
-    });
-    if (host) return r;
-    return single_query(mb, in, 1, 6 * n, [&](double *din, double *dout, hipStream_t s) {
-        const double *mdl = nullptr;
-        int rc = device_consts<double>(mb, &mdl);
-        if (rc) return rc;
-        hipError_t e = launch_kin_any<double>(mb, true, mdl, din, dout, 1, 1, s);
-        return e == hipSuccess ? RB_OK : hip_err(e, "jac launch");
-    });
+    return single_config(
+        mb, {q}, 6 * n, "jac launch", [&](double *o) { return rbamd::host_jac(mb->model, mb->pk64.data(), q, o); },
+        [&](const double *mdl, double *din, double *dout, hipStream_t s) {
+            return launch_kin_any<double>(mb, true, mdl, din, dout, 1, 1, s);
+        });
 }
 
 // ---------------------------------------------------------------- model handling
@@ -974,20 +833,8 @@ int multibody_topology(const Multibody *mb, int *parent, int *joint_type) {
 
 // C++ helpers of the kernel-inspection entry points below
 namespace {
-// The kernel a launch of `batch` configurations of `kind` takes: the same resolution as the
-// launchers (launch_*_any).  *generic = true when the precompiled kernel runs (serial revolute
-// fwd_kin / jac, JIT disabled or failed).
-const rbamd::JitKernel *resolve_kernel(const Multibody *mb, int kind, bool f64, int64_t batch, bool tiled) {
-    if ((kind == 4 || kind == 5) && kin_precompiled(mb)) return nullptr;  // precompiled kinematics
-    if (!rbamd::jit_enabled()) return nullptr;
-    const uint32_t B = batch < kChunk ? (uint32_t)batch : (uint32_t)kChunk;
-    if (kind == 0) return jit_rnea(mb, f64, B, tiled);
-    if (kind == 1) return jit_fd(mb, f64, B);
-    if (kind == 3) return jit_rollout(mb, f64, B);
-    if (kind == 6) return jit_idfd(mb, f64, B);
-    if (kind >= 4) return jit_kin(mb, kind == 5, f64);
-    return jit_get(mb, rbamd::JitKind::Crba, f64, false);
-}
+// The size of the (first) launch a call of `batch` configurations makes (chunked).
+uint32_t launch_size(int64_t batch) { return batch < kChunk ? (uint32_t)batch : (uint32_t)kChunk; }
 
 int check_kernel_query(const Multibody *mb, int kind, int64_t batch) {
     if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
@@ -996,30 +843,21 @@ int check_kernel_query(const Multibody *mb, int kind, int64_t batch) {
     return RB_OK;
 }
 
-// The (pack, tail) jit_get resolves a shape to (the kernel's actual form).
-void resolve_pack(const Multibody *mb, rbamd::JitKind kind, bool f64, const JitShape &sh, int *pk, int *tl) {
-    *pk = sh.pack > 0 ? sh.pack : rbamd::jit_model_pack(mb->model, kind, f64, 0);
-    *tl = (kind == rbamd::JitKind::Rnea && *pk == 3) ? sh.tail : 0;
-}
-
 // The hipRTC source of the kernel a launch of `batch` configurations (tiled or SoA) would run:
 // compiled here (hipRTC, gfx950, no device needed) so that the occupancy-cliff rebuild of
 // jit_compile shows in it -- the source of the code object a launch really loads; the generated
 // source as it stands if hipRTC fails.
 std::string shaped_source(const Multibody *mb, int kind, bool f64, int64_t batch, bool tiled) {
-    const uint32_t B = batch < kChunk ? (uint32_t)batch : (uint32_t)kChunk;
-    const auto k = (rbamd::JitKind)kind;
-    const JitShape sh = jit_shape(mb, k, f64, B, tiled);
-    int pk = 0, tl = 0;
-    resolve_pack(mb, k, f64, sh, &pk, &tl);
+    const rbamd::JitVariant v =
+        rbamd::jit_resolve(mb->model, (rbamd::JitKind)kind, f64, launch_size(batch), tiled, fast_trig());
     // the length query and the copy of multibody_jit_source_ex come in pairs: one compile for both
     thread_local std::string t_key, t_src;
-    const std::string plain = rbamd::jit_source(mb->model, k, f64, sh.fast, pk, tl, sh.nt);
+    const std::string plain = rbamd::jit_source(mb->model, v, -1);
     const std::string key = std::to_string((uintptr_t)mb) + ":" + std::to_string(rbamd::tuning_generation()) + ":" + plain;
     if (key == t_key) return t_src;
     std::vector<char> code;
     std::string err, src;
-    if (!rbamd::jit_compile(mb->model, k, f64, sh.fast, "gfx950", &code, &err, pk, tl, sh.nt, &src)) src = plain;
+    if (!rbamd::jit_compile(mb->model, v, "gfx950", &code, &err, &src)) src = plain;
     t_key = key;
     t_src = src;
     return src;
@@ -1036,15 +874,15 @@ extern "C" {
 
 int multibody_kernel_path_ex(const Multibody *mb, int kind, int f64, int64_t batch, int tiled) {
     if (int rc = check_kernel_query(mb, kind, batch)) return -rc;
-    if (resolve_kernel(mb, kind, f64 != 0, batch, tiled != 0)) return 1;
+    if (kernel_for(mb, (rbamd::JitKind)kind, f64 != 0, launch_size(batch), tiled != 0)) return 1;
     if (rbamd::jit_enabled() && !((kind == 4 || kind == 5) && kin_precompiled(mb))) note_jit_errors(mb);
     return 0;
 }
 
 int multibody_kernel_form_ex(const Multibody *mb, int kind, int f64, int64_t batch, int tiled) {
     if (int rc = check_kernel_query(mb, kind, batch)) return -rc;
-    const rbamd::JitKernel *jk = resolve_kernel(mb, kind, f64 != 0, batch, tiled != 0);
-    return jk ? jk->pack : 0;
+    const rbamd::JitKernel *jk = kernel_for(mb, (rbamd::JitKind)kind, f64 != 0, launch_size(batch), tiled != 0);
+    return jk ? jk->variant.pack : 0;
 }
 
 int multibody_kernel_path(const Multibody *mb, int kind, int f64) {
@@ -1079,15 +917,11 @@ int64_t multibody_jit_compile(const Multibody *mb, int kind, int f64, const char
 
 int64_t multibody_jit_compile_ex(const Multibody *mb, int kind, int f64, int64_t batch, int tiled, const char *arch) {
     if (int rc = check_kernel_query(mb, kind, batch)) return -rc;
-    const uint32_t B = batch < kChunk ? (uint32_t)batch : (uint32_t)kChunk;
-    const auto k = (rbamd::JitKind)kind;
-    const JitShape sh = jit_shape(mb, k, f64 != 0, B, tiled != 0);
-    int pk = 0, tl = 0;
-    resolve_pack(mb, k, f64 != 0, sh, &pk, &tl);
+    const rbamd::JitVariant v =
+        rbamd::jit_resolve(mb->model, (rbamd::JitKind)kind, f64 != 0, launch_size(batch), tiled != 0, fast_trig());
     std::vector<char> code;
     std::string err;
-    if (!rbamd::jit_compile(mb->model, k, f64 != 0, sh.fast, arch ? arch : "gfx950", &code, &err, pk, tl, sh.nt))
-        return -set_err(RB_ERR_HIP, err);
+    if (!rbamd::jit_compile(mb->model, v, arch ? arch : "gfx950", &code, &err)) return -set_err(RB_ERR_HIP, err);
     return (int64_t)code.size();
 }
 

@@ -42,7 +42,8 @@ std::string literal(double x, bool f64) {
     return s;
 }
 
-}  // namespace
+// ---- policy: which kernel variant a launch takes (jit_resolve) and what each variant's source
+// and compile flags are made of.  Every tuning knob read here is part of jit_key.
 
 int jit_nt(JitKind kind) {
     if (kind == JitKind::Rnea) return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
@@ -65,15 +66,8 @@ bool jit_opaque(JitKind kind, bool f64, int n) {
     return n <= 16 && kind == JitKind::Rollout && !(f64 && n <= 8);
 }
 
-int jit_waves(JitKind kind, bool f64, int n) {
-    const int v = tuning().jit_waves;
-    if (v >= 0) return v;
-    if (kind == JitKind::Rollout && !f64 && n <= 8) return jit_pack(kind, f64, n) != 1 ? 2 : 4;
-    // (the fp64 rollout of the mass-matrix form takes a 4-wave target in jit_source; the ABA
-    // form -- the rollout of trees, or fd_form 1 -- none: 436 B of scratch per lane under it)
-    return 0;
-}
-
+// Configurations per lane of `kind`'s lane kernel under the tuning `pack` alone (jit_resolve
+// adds the batch rules, jit_model_pack what the model allows).
 int jit_pack(JitKind kind, bool f64, int n) {
     // 2 = two configurations per lane on packed fp32 (fp32 forward dynamics of chains up to 8
     // links: FR3 2^20 tiled 28.7 vs 30.7 us; 200+ VGPRs for the pair, 2 waves/SIMD; the
@@ -99,9 +93,33 @@ int jit_pack(JitKind kind, bool f64, int n) {
     return (!f64 && n <= 8) ? 2 : 1;
 }
 
+int jit_waves(JitKind kind, bool f64, int n) {
+    const int v = tuning().jit_waves;
+    if (v >= 0) return v;
+    if (kind == JitKind::Rollout && !f64 && n <= 8) return jit_pack(kind, f64, n) != 1 ? 2 : 4;
+    // (the fp64 rollout of the mass-matrix form takes a 4-wave target in jit_source; the ABA
+    // form -- the rollout of trees, or fd_form 1 -- none: 436 B of scratch per lane under it)
+    return 0;
+}
+
 bool jit_f64_tab(bool f64) { return f64 && tuning().f64_tab != 0; }
 
-int jit_fd_form(const Model &m, JitKind kind) {
+// Percent of a sequential-pair RNEA launch's tiles run one per lane for this layout (tuning
+// seq_tail; auto: 75 for the tiled layout, 0 for SoA).
+int jit_seq_tail(bool tiled) {
+    const int v = tuning().seq_tail;
+    if (v < 0) return tiled ? 75 : 0;
+    return v < 100 ? v : 100;
+}
+
+// What the model-dependent rules below read of the model.  jit_resolve runs on every launch and
+// serial_revolute() walks the links, so it is read once per resolve.
+struct ModelShape {
+    int n;
+    bool serial;
+};
+
+int fd_form(const ModelShape &m, JitKind kind) {
     // 2 = mass-matrix forward dynamics (fdh_body.hip.hpp: RNEA bias + CRBA + L D L^T), 1 = the
     // Articulated-Body Algorithm (aba_body.hip.hpp).  The mass-matrix form holds ~n^2/2 values
     // per lane where the ABA holds ~12 per link across its sweeps, so it runs at 2-3x the
@@ -114,42 +132,146 @@ int jit_fd_form(const Model &m, JitKind kind) {
     const int v = tuning().fd_form;
     // trees: the mass-matrix form only for forward dynamics and only on request (fdh_eval_tree;
     // A/B), rollouts and the wave splits / pairs are serial-chain forms
-    if (!m.serial_revolute()) return (kind == JitKind::Fd && v == 2) ? 2 : 1;
+    if (!m.serial) return (kind == JitKind::Fd && v == 2) ? 2 : 1;
     if (v == 1 || v == 2) return v;
     return m.n <= (kind == JitKind::Rollout ? 8 : 12) ? 2 : 1;
 }
 
-int jit_seq_tail(bool tiled) {
-    const int v = tuning().seq_tail;
-    if (v < 0) return tiled ? 75 : 0;
-    return v < 100 ? v : 100;
-}
+}  // namespace
 
-int jit_model_pack(const Model &m, JitKind kind, bool f64, int pack_req) {
+int jit_fd_form(const Model &m, JitKind kind) { return fd_form({m.n, m.serial_revolute()}, kind); }
+
+namespace {
+
+// The lane form a kernel of this model really takes for the requested pack (0 = the jit_pack policy).
+int jit_model_pack(const ModelShape &m, JitKind kind, bool f64, int pack_req) {
     const int pack = pack_req > 0 ? pack_req : jit_pack(kind, f64, m.n);
-    // the tree form of the mass-matrix forward dynamics is one configuration per lane
-    if (kind == JitKind::Fd && !m.serial_revolute() && jit_fd_form(m) == 2) return 1;
-    // the mass-matrix forward dynamics has one- and two-per-lane forms only
-    if (kind == JitKind::Fd && pack == 3 && jit_fd_form(m) == 2) return 1;
+    if (kind == JitKind::Fd) {
+        const bool fdh = fd_form(m, kind) == 2;
+        // the tree form of the mass-matrix forward dynamics is one configuration per lane
+        if (!m.serial && fdh) return 1;
+        // the mass-matrix forward dynamics has one- and two-per-lane forms only
+        if (pack == 3 && fdh) return 1;
+    }
     // 4 / 5 = the bias / mass-matrix wave split, packed / one per lane: fp32 mass-matrix FD only
-    if (pack == 4 && kind == JitKind::Rollout && !(!f64 && jit_fd_form(m, kind) == 2 && !(tuning().jit_variant & 256)))
+    if (pack == 4 && kind == JitKind::Rollout && !(!f64 && fd_form(m, kind) == 2 && !(tuning().jit_variant & 256)))
         return (!f64 && m.n <= 8) ? 2 : 1;  // the split needs the mass-matrix form: the pair instead
-    if (pack == 4 && kind != JitKind::Rollout && !(kind == JitKind::Fd && !f64 && jit_fd_form(m) == 2)) return 1;
-    if (pack == 5 && !((kind == JitKind::Fd || kind == JitKind::RneaFd) && jit_fd_form(m) == 2 && m.serial_revolute()))
+    if (pack == 4 && kind != JitKind::Rollout && !(kind == JitKind::Fd && !f64 && fd_form(m, JitKind::Fd) == 2)) return 1;
+    if (pack == 5 && !((kind == JitKind::Fd || kind == JitKind::RneaFd) && fd_form(m, JitKind::Fd) == 2 && m.serial))
         return 1;
     return pack;
 }
 
-std::string jit_tag(JitKind kind, bool f64, int n) {
+// ---- the lane form a launch of B configurations asks for while the tuning `pack` is unset
+// (the auto policy); 0 = the jit_pack policy.  jit_model_pack then clamps it to the model.
+
+// Smallest batch for which the auto policy takes the sequential-pair fp64 RNEA (jit_pack 3):
+// it halves the waves, so below two resident rounds of the one-per-lane kernel (4 waves/SIMD x
+// 1024 SIMDs x 64 lanes x 2) the one-per-lane kernel keeps more of the chip busy.
+constexpr uint32_t kSeqMinBatch = 1u << 19;
+
+// fp32 chains up to 8 links on the tiled layout at large batches: the sequential pair too
+// (FR3 2^20 22.0-22.1 vs 22.3-24.0 us on two boxes, profiles/r04/ab/ab_r32_seq*.log), with
+// ordinary (temporal) loads and stores (tuning.hpp rnea_nt; the 30-link chain and the 14-DOF
+// tree keep nt = 3)
+bool rnea_big32(const ModelShape &m, bool f64, uint32_t B, bool tiled) {
+    return !f64 && tiled && B >= kSeqMinBatch && m.n <= 8;
+}
+
+int rnea_pack(const ModelShape &m, bool f64, uint32_t B, bool tiled) {
+    return tuning().pack >= 0 ? 0 : rnea_big32(m, f64, B, tiled) ? 3 : B < kSeqMinBatch ? 1 : 0;
+}
+
+// Smallest batch for which the auto policy takes the paired-lane kernel: one resident round
+// of it (2 blocks of 512 configurations per CU x 256 CUs) -- 2^18.
+constexpr uint32_t kPackMinBatch = 1u << 18;
+// fp32 mass-matrix forward dynamics at small batches: one wave per SIMD at most, so the launch
+// time follows each wave's instruction stream; the wave splits (fdh_body.hip.hpp) halve it.
+// Up to 2^17 configurations the one-per-lane split (pack 5: B/32 waves, its roles alternating
+// over the SIMDs), above it the packed pair; the packed split (pack 4: B/64 waves) is the
+// rollout's, with the same bound.  FR3, HIP graph (profiles/r06/mix/): 32768 3.53 us (pack 5)
+// / 3.99 (4); 65536 4.15 (5) / 4.24 (4); 131072 5.45 (5) / 5.50 (4).
+constexpr uint32_t kSplitMaxBatch = 1u << 17;
+
+// The forward-dynamics kernel a launch of B configurations takes (auto policy when the
+// tuning `pack` is unset).
+int fd_pack(const ModelShape &m, bool f64, uint32_t B) {
+    int pack = 0;
+    if (tuning().pack < 0) {
+        if (!f64 && fd_form(m, JitKind::Fd) == 2 && m.n <= 8 && m.serial)  // splits: serial chains, measured on FR3
+            pack = B <= kSplitMaxBatch ? 5 : 0;
+        else  // paired lanes halve the grid: below kPackMinBatch one per lane fills more CUs
+            pack = B < kPackMinBatch ? 1 : 0;
+    }
+    return pack;
+}
+
+// The rollout kernel a launch of B configurations takes: fp32 mass-matrix rollouts up to 2^17
+// configurations split every step over a pair of packed waves (aba_body.hip.hpp
+// rollout_split_block2), as fd_pack's small-batch forward dynamics.  FR3, K = 16, HIP graph:
+// 16384 43.3 vs 62.7 us (pair), 65536 43.6 vs 63.5, 131072 58.9 vs 63.7; 262144 101.5 vs 93.2
+// (profiles/r03/rollout_split/).
+int rollout_pack(const ModelShape &m, bool f64, uint32_t B) {
+    return (tuning().pack < 0 && !f64 && B <= kSplitMaxBatch && fd_form(m, JitKind::Rollout) == 2 &&
+            !(tuning().jit_variant & 256)) ? 4 : 0;
+}
+
+// The fused pair's kernel form for B configurations (auto policy when the tuning `pack` is
+// unset): the wave split (pack 5, idfd_split_block1) for fp32 up to 2^16 configurations, one
+// per lane otherwise.  FR3, HIP graph, tiled (profiles/r06/split/): fp32 65536 4.82 vs 5.24 us,
+// 131072 6.79 vs 6.49; fp64 65536 6.64 vs 6.70, 131072 11.55 vs 10.67, 262144 22.06 vs 20.59 --
+// as for the forward dynamics alone (fp64 FD split 10.16 vs 8.62 us at 2^17): the SIMDs already
+// hold 2 waves of the one-per-lane kernel there, and the split repeats the loads and sincos.
+// With the split's roles alternating over the SIMDs (round 6, profiles/r06/mix/): fp32 65536
+// 4.75 us, 131072 6.53 vs 6.46 one per lane -- the bound stays.
+constexpr uint32_t kIdfdSplitMaxBatch32 = 1u << 16;
+int idfd_pack(bool f64, uint32_t B) {
+    if (tuning().pack >= 0) return 0;
+    return (!f64 && B <= kIdfdSplitMaxBatch32) ? 5 : 1;
+}
+
+}  // namespace
+
+JitVariant jit_resolve(const Model &model, JitKind kind, bool f64, uint32_t B, bool tiled, bool fast_trig) {
+    // only the forward-dynamics kinds' rules read `serial`: the others do not pay for the walk
+    const bool fd_kind = kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd;
+    const ModelShape m{model.n, fd_kind && model.serial_revolute()};
+    JitVariant v;
+    v.kind = kind;
+    v.f64 = f64;
+    // CRBA evaluates its angles with the precise fp32 sincos; every other kind with the fast one
+    // unless RB_FAST_TRIG=0 (fp64 always its own)
+    v.fast = kind != JitKind::Crba && fast_trig && !f64;
+    int pack_req = 0;
+    switch (kind) {
+        case JitKind::Rnea:
+            pack_req = rnea_pack(m, f64, B, tiled);
+            v.nt = (rnea_big32(m, f64, B, tiled) && tuning().rnea_nt < 0) ? 0 : -1;
+            break;
+        case JitKind::Fd: pack_req = fd_pack(m, f64, B); break;
+        case JitKind::Rollout: pack_req = rollout_pack(m, f64, B); break;
+        case JitKind::RneaFd: pack_req = idfd_pack(f64, B); break;
+        default: break;
+    }
+    v.pack = jit_model_pack(m, kind, f64, pack_req);
+    if (kind == JitKind::Rnea && v.pack == 3) v.tail = jit_seq_tail(tiled);
+    return v;
+}
+
+std::string jit_key(const Model &m, const JitVariant &v) {
+    const JitKind kind = v.kind;
+    const bool f64 = v.f64;
     // ":w" the policy's target, ":W" the raw knob (-1 lets jit_compile rebuild at the occupancy cliff)
-    return ":nt" + std::to_string(jit_nt(kind)) + ":w" + std::to_string(jit_waves(kind, f64, n)) + ":W" +
+    return ":k" + std::to_string((int)kind) + (f64 ? ":f64" : ":f32") + (v.fast ? ":fast" : ":precise") + ":nt" +
+           std::to_string(jit_nt(kind)) + ":w" + std::to_string(jit_waves(kind, f64, m.n)) + ":W" +
            std::to_string(tuning().jit_waves.load()) + ":o" +
-           std::to_string(jit_opaque(kind, f64, n) ? 1 : 0) + ":p" + std::to_string(jit_pack(kind, f64, n)) +
+           std::to_string(jit_opaque(kind, f64, m.n) ? 1 : 0) + ":p" + std::to_string(jit_pack(kind, f64, m.n)) +
            ":t" + std::to_string(jit_f64_tab(f64) ? 1 : 0) + ":r" + std::to_string(tuning().split_rot) + ":v" +
            std::to_string(tuning().jit_variant) + ":f" + std::to_string(tuning().fd_form) + ":k" +
            std::to_string(kind == JitKind::Rnea ? tuning().rnea_park.load() : 0) + ":e" +
            std::to_string(kind == JitKind::Rnea ? tuning().rnea_rev.load() : 0) + ":a" +
-           std::to_string(tuning().kernarg_preload.load());
+           std::to_string(tuning().kernarg_preload.load()) + ":q" + std::to_string(v.pack) + ":st" +
+           std::to_string(v.tail) + ":n" + std::to_string(v.nt);
 }
 
 int code_vgprs(const std::vector<char> &code) {
@@ -167,44 +289,31 @@ int code_vgprs(const std::vector<char> &code) {
     return -1;
 }
 
-std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pack_req, int tail, int nt,
-                       int waves_req) {
+// The paired fp32 rollout and the fp64 rollout of short chains keep 2 waves/SIMD only
+// without machine LICM: hoisting per-step address arithmetic and constants out of the K
+// loop costs the VGPRs below 256 (fp64 FR3: 212 instead of 264).
+static bool jit_no_licm(const Model &m, const JitVariant &v) {
+    return v.kind == JitKind::Rollout && jit_rollout_no_hoist(v.f64, m.n, v.pack);
+}
+
+std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
+    const JitKind kind = v.kind;
+    const bool f64 = v.f64;
+    const int pack = v.pack;
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
         double *c = &pk[(size_t)i * kLinkStride];
         for (int k = 0; k < 9; ++k) c[kE0 + k] = snap(c[kE0 + k]);
         for (int k = 0; k < 3; ++k) c[kP + k] = snap(c[kP + k]);
     }
-    const char *F = fast ? "true" : "false";
-    const int pack = jit_model_pack(m, kind, f64, pack_req);
+    const char *F = v.fast ? "true" : "false";
+
+    // ---- what this variant's source is made of, decided before any text is written
     const bool fdh = (kind == JitKind::Fd || kind == JitKind::RneaFd) && jit_fd_form(m) == 2;
-    std::ostringstream o;
-    o << "#define RB_NT " << (nt >= 0 ? nt : jit_nt(kind)) << "\n";
-    o << "#define RB_VARIANT " << tuning().jit_variant << "\n";
-    o << "#define RB_OPAQUE_CONSTS " << (jit_opaque(kind, f64, m.n) ? 1 : 0) << "\n";
-    if (kind == JitKind::Rollout && jit_rollout_no_hoist(f64, m.n, pack)) o << "#define RB_ROLLOUT_NO_HOIST 1\n";
-    // input checks pinned into the sweep's state (rnea_body.hip.hpp rnea_fwd)
-    if (kind == JitKind::Rollout || m.n > 8) o << "#define RB_GUARD_ANCHOR 1\n";
     // the rollout's forward dynamics follows the fd_form policy (mass-matrix form for short
     // serial chains) unless RB_VARIANT bit 8 (A/B) keeps the ABA
-    if (kind == JitKind::Rollout && jit_fd_form(m, kind) == 2 && !(tuning().jit_variant & 256))
-        o << "#define RB_ROLLOUT_FDH 1\n";
+    const bool rollout_fdh = kind == JitKind::Rollout && jit_fd_form(m, kind) == 2 && !(tuning().jit_variant & 256);
     const bool tab = jit_f64_tab(f64);
-    o << "#define RB_SINCOS_TAB " << (tab ? 1 : 0) << "\n";
-    if (tab) {  // (cos, sin)(k pi/128), k < 256, for sincos_tab (spatial.hip.hpp): long double, quadrants exact
-        const long double pi = 3.141592653589793238462643383279502884L;
-        o << "static __device__ constexpr double rb_sctab_src[512] = {\n";
-        for (int k = 0; k < 256; ++k) {
-            double c = (double)std::cos((long double)k * pi / 128.0L), s = (double)std::sin((long double)k * pi / 128.0L);
-            if (k % 64 == 0) {
-                const int q = k / 64;
-                c = q == 0 ? 1.0 : q == 2 ? -1.0 : 0.0;
-                s = q == 1 ? 1.0 : q == 3 ? -1.0 : 0.0;
-            }
-            o << "  " << literal(c, true) << ", " << literal(s, true) << ",\n";
-        }
-        o << "};\n";
-    }
     // Split joint rotation (artinertia.hip.hpp to_parent_split): pays only when every R_p is a
     // signed permutation (its congruence then folds away); a dense constant R_p (general-axis
     // frames, trees) makes it costlier than the folded E S E^T.
@@ -213,14 +322,14 @@ std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pa
         for (int r = 0; r < 3; ++r) {
             int ones = 0;
             for (int c = 0; c < 3; ++c) {
-                const double v = pk[(size_t)i * kLinkStride + kE0 + 3 * r + c];
-                if (v == 1.0 || v == -1.0) ++ones;
-                else if (v != 0.0) perm = false;
+                const double e = pk[(size_t)i * kLinkStride + kE0 + 3 * r + c];
+                if (e == 1.0 || e == -1.0) ++ones;
+                else if (e != 0.0) perm = false;
             }
             if (ones != 1) perm = false;
         }
     const int sr = tuning().split_rot;
-    o << "#define RB_SPLIT_ROT " << ((sr > 0 || (sr < 0 && perm)) ? 1 : 0) << "\n";
+    const bool split_rot = sr > 0 || (sr < 0 && perm);
     // Newton-Euler link forces about the centre of mass (spatial.hip.hpp link_force) for the
     // RNEA sweeps of chains and trees (and so the mass-matrix FD's bias): c = h / m and
     // Ic = I_o - m (|c|^2 1 - c c^T) per link (massless virtual links: c = 0, Ic = I_o = 0), in
@@ -245,8 +354,48 @@ std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pa
     // hipRTC to fail on (which would leave the launch on the generic kernel)
     constexpr int kMaxPark = (160 * 1024 / 3) / (4 * 6 * 64 * 4);
     const int pk_req = std::min(kMaxPark, tuning().rnea_park < 0 ? (m.n >= 20 ? 8 : 0) : tuning().rnea_park.load());
-    const int park = (kind == JitKind::Rnea && !f64 && pack == 1 && m.serial_revolute() && com &&
-                      (sr > 0 || (sr < 0 && perm)) && pk_req > 0 && pk_req < m.n) ? pk_req : 0;
+    const int park = (kind == JitKind::Rnea && !f64 && pack == 1 && m.serial_revolute() && com && split_rot &&
+                      pk_req > 0 && pk_req < m.n) ? pk_req : 0;
+    // The occupancy target: a request, else the jit_waves policy, else (the knob unset) 4 for
+    // three forms.  The paired mass-matrix FD fits 4 waves/SIMD at exactly 128 VGPRs with the
+    // occupancy target (130 and 3 waves without): FR3 2^20 tiled 26.4 vs 27.0 us.
+    int waves = waves_req >= 0 ? waves_req : jit_waves(kind, f64, m.n);
+    const bool waves_auto = tuning().jit_waves < 0 && waves_req < 0;
+    if (fdh && pack == 2 && waves_auto) waves = 4;
+    // fp64 rollout of the mass-matrix form: 127 VGPRs, 4 waves/SIMD either way since the input
+    // checks; the target keeps it there (FR3 2^20 x 16 steps, reset state: 690-708 vs 702-704 us,
+    // noise-level).  Not for the ABA form: 256 VGPRs at 1 wave/SIMD runs 984 us, 2 / 3 / 4-wave
+    // targets spill (1068 / 2756 / 4131 us; profiles/r05/ab/rollout_forms/).
+    if (rollout_fdh && f64 && m.n <= 8 && waves_auto) waves = 4;
+    if (kind == JitKind::Rnea && f64 && (tuning().jit_variant & 32768) && waves_auto) waves = 4;  // A/B
+    // the parked kernel's own target, whatever was asked.  park > 0 means fp32 and pack 1, so
+    // neither the reversed form (fp64) nor the sequential pair is emitted instead of it.
+    if (park > 0) waves = 3;
+
+    std::ostringstream o;
+    o << "#define RB_NT " << (v.nt >= 0 ? v.nt : jit_nt(kind)) << "\n";
+    o << "#define RB_VARIANT " << tuning().jit_variant << "\n";
+    o << "#define RB_OPAQUE_CONSTS " << (jit_opaque(kind, f64, m.n) ? 1 : 0) << "\n";
+    if (jit_no_licm(m, v)) o << "#define RB_ROLLOUT_NO_HOIST 1\n";
+    // input checks pinned into the sweep's state (rnea_body.hip.hpp rnea_fwd)
+    if (kind == JitKind::Rollout || m.n > 8) o << "#define RB_GUARD_ANCHOR 1\n";
+    if (rollout_fdh) o << "#define RB_ROLLOUT_FDH 1\n";
+    o << "#define RB_SINCOS_TAB " << (tab ? 1 : 0) << "\n";
+    if (tab) {  // (cos, sin)(k pi/128), k < 256, for sincos_tab (spatial.hip.hpp): long double, quadrants exact
+        const long double pi = 3.141592653589793238462643383279502884L;
+        o << "static __device__ constexpr double rb_sctab_src[512] = {\n";
+        for (int k = 0; k < 256; ++k) {
+            double c = (double)std::cos((long double)k * pi / 128.0L), s = (double)std::sin((long double)k * pi / 128.0L);
+            if (k % 64 == 0) {
+                const int q = k / 64;
+                c = q == 0 ? 1.0 : q == 2 ? -1.0 : 0.0;
+                s = q == 1 ? 1.0 : q == 3 ? -1.0 : 0.0;
+            }
+            o << "  " << literal(c, true) << ", " << literal(s, true) << ",\n";
+        }
+        o << "};\n";
+    }
+    o << "#define RB_SPLIT_ROT " << (split_rot ? 1 : 0) << "\n";
     if (com) {
         o << "#define RB_COM_FORM 1\n";
         o << "static __device__ constexpr double rb_com[" << 9 * m.n << "] = {\n";
@@ -304,6 +453,33 @@ std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pa
         for (size_t k = 0; k < pk.size(); ++k) o << "  " << literal(pk[k], f64) << ",\n";
     }
     o << "};\n";
+    // ---- the kernel: one signature helper, one prologue per lane form
+    const std::string head = std::string("extern \"C\" __global__ __launch_bounds__(256) ") +
+                             (waves ? "__attribute__((amdgpu_waves_per_eu(" + std::to_string(waves) + "))) " : "") + "void ";
+    auto sig = [&](const std::string &params) { o << head << "rb_jit_kernel(" << params << ") {\n"; };
+    // Lane kernels take the block stride bs (elements): 256 for SoA, N * 256 for the tiled
+    // layout (kernels.hpp); block k's arrays start at element k * bs, lane offset threadIdx.x.
+    auto dyn_params = [](const char *in3, const char *out) {  // dynamics: three inputs, one output
+        return std::string("const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ ") + in3 +
+               ", T *__restrict__ " + out + ", uint32_t B, int64_t ld, int64_t bs";
+    };
+    const char *fused_params =
+        "const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ qdd, const T *__restrict__ tau_in, "
+        "T *__restrict__ tau, T *__restrict__ qdd_out, uint32_t B, int64_t ld, int64_t bs";
+    const char *rollout_params =
+        "T *__restrict__ q, T *__restrict__ qd, const T *__restrict__ tau_seq, T dt, int K, T *__restrict__ traj, "
+        "uint32_t B, int64_t ld";
+    // q-only kernels take the block strides of their input and output rows (256 for SoA;
+    // n * 256 / rows * 256 for the tiled layout), as the lane kernels above
+    auto q_params = [](const char *out) {
+        return std::string("const T *__restrict__ q, T *__restrict__ ") + out +
+               ", uint32_t B, int64_t ld, int64_t bs_in, int64_t bs_out";
+    };
+    // One configuration per lane: lane t of block k is configuration 256 k + t.
+    const std::string lane_guard =
+        "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n"
+        "  if (b >= B) return;\n";
+    const std::string lane_prologue = lane_guard + "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
     // Paired lanes: block k owns batch blocks 2k and 2k+1 (SoA: configurations 512k + t and
     // 512k + 256 + t; tiled: lane t of tiles 2k and 2k+1).  When the second is past B, the
     // lane evaluates the first twice and stores the bit-identical value twice.
@@ -315,156 +491,94 @@ std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pa
         "  const uint32_t offB = bA + 256u < B ? offA + (uint32_t)bs * 4u : offA;\n";
     // Sequential pair (pack 3): lane t of batch blocks 2k and 2k+1, evaluated one after the
     // other from one load burst; the second only when it exists (twoB).
-    const std::string seq_prologue =
+    const char *seq_prologue =
         "  const uint32_t bA = blockIdx.x * 512u + threadIdx.x;\n"
         "  if (bA >= B) return;\n"
         "  const int64_t oA = (int64_t)(2u * blockIdx.x) * bs;\n"
         "  const uint32_t offA = threadIdx.x * (uint32_t)sizeof(T);\n"
         "  const bool twoB = bA + 256u < B;\n"
         "  const uint32_t offB = offA + (uint32_t)bs * (uint32_t)sizeof(T);\n";
-    std::string head_s = "extern \"C\" __global__ __launch_bounds__(256) ";
-    // The paired mass-matrix FD fits 4 waves/SIMD at exactly 128 VGPRs with the occupancy
-    // target (130 and 3 waves without): FR3 2^20 tiled 26.4 vs 27.0 us.
-    int waves = waves_req >= 0 ? waves_req : jit_waves(kind, f64, m.n);
-    if (fdh && pack == 2 && tuning().jit_waves < 0 && waves_req < 0) waves = 4;
-    // fp64 rollout of the mass-matrix form: 127 VGPRs, 4 waves/SIMD either way since the input
-    // checks; the target keeps it there (FR3 2^20 x 16 steps, reset state: 690-708 vs 702-704 us,
-    // noise-level).  Not for the ABA form: 256 VGPRs at 1 wave/SIMD runs 984 us, 2 / 3 / 4-wave
-    // targets spill (1068 / 2756 / 4131 us; profiles/r05/ab/rollout_forms/).
-    if (kind == JitKind::Rollout && f64 && m.n <= 8 && jit_fd_form(m, kind) == 2 && !(tuning().jit_variant & 256) &&
-        tuning().jit_waves < 0 && waves_req < 0)
-        waves = 4;
-    if (kind == JitKind::Rnea && f64 && (tuning().jit_variant & 32768) && tuning().jit_waves < 0 && waves_req < 0)
-        waves = 4;  // A/B
-    if (const int w = waves)
-        head_s += "__attribute__((amdgpu_waves_per_eu(" + std::to_string(w) + "))) ";
-    head_s += "void ";
-    const char *head = head_s.c_str();
-    // Lane kernels take the block stride bs (elements): 256 for SoA, N * 256 for the tiled
-    // layout (kernels.hpp); block k's arrays start at element k * bs, lane offset threadIdx.x.
-    if (kind == JitKind::Rnea && pack == 3 && tail > 0) {
-        // pairs of tiles for blocks < G1, then one tile per block for the last S tiles
-        o << head << "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ qdd, T *__restrict__ tau, uint32_t B, int64_t ld, int64_t bs) {\n";
-        o << "  const uint32_t T_ = (B + 255u) / 256u, S_ = (uint32_t)(((uint64_t)T_ * " << tail
-          << "u) / 100u);\n";
-        o << "  const uint32_t P_ = (T_ - S_) & ~1u, G1 = P_ / 2u;\n";
-        o << "  if (blockIdx.x >= G1) {\n";
-        o << "    const uint32_t t = P_ + (blockIdx.x - G1), b = t * 256u + threadIdx.x;\n";
-        o << "    if (b >= B) return;\n";
-        o << "    const int64_t o = (int64_t)t * bs;\n";
-        o << "    rbamd::dev::rnea_lane<T, N, " << F
-          << ", Topo>(kModel, q + o, qd + o, qdd + o, tau + o, threadIdx.x, ld);\n    return;\n  }\n";
-        o << seq_prologue;
-        o << "  rbamd::dev::rnea_lane_seq2<T, N, " << F
-          << ", Topo>(kModel, q + oA, qd + oA, qdd + oA, tau + oA, offA, offB, twoB, ld);\n}\n";
-    } else if (kind == JitKind::Rnea && pack == 3) {
-        o << head << "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ qdd, T *__restrict__ tau, uint32_t B, int64_t ld, int64_t bs) {\n";
-        o << seq_prologue;
-        o << "  rbamd::dev::rnea_lane_seq2<T, N, " << F
-          << ", Topo>(kModel, q + oA, qd + oA, qdd + oA, tau + oA, offA, offB, twoB, ld);\n}\n";
-    } else if (kind == JitKind::Rnea && rev && com && pack == 1) {
-        o << head << "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ qdd, T *__restrict__ tau, uint32_t B, int64_t ld, int64_t bs) {\n";
-        o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-        o << "  if (b >= B) return;\n";
-        o << "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
-        o << "  rbamd::dev::rnea_lane_rev<T, N, " << F << ">(kModel, q + o, qd + o, qdd + o, tau + o, threadIdx.x, ld);\n}\n";
-    } else if (kind == JitKind::Rnea && park > 0) {
-        o << "extern \"C\" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void "
-             "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ qdd, T *__restrict__ tau, uint32_t B, int64_t ld, int64_t bs) {\n";
-        o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-        o << "  if (b >= B) return;\n";
-        o << "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
-        o << "  rbamd::dev::rnea_lane_park<T, N, " << F << ", " << park
-          << ">(kModel, q + o, qd + o, qdd + o, tau + o, threadIdx.x, ld);\n}\n";
-    } else if (kind == JitKind::Rnea) {
-        o << head << "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ qdd, T *__restrict__ tau, uint32_t B, int64_t ld, int64_t bs) {\n";
-        o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-        o << "  if (b >= B) return;\n";
-        o << "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
-        o << "  rbamd::dev::rnea_lane<T, N, " << F << ", Topo>(kModel, q + o, qd + o, qdd + o, tau + o, threadIdx.x, ld);\n}\n";
+    if (kind == JitKind::Rnea) {
+        sig(dyn_params("qdd", "tau"));
+        const char *lane_args = "(kModel, q + o, qd + o, qdd + o, tau + o, threadIdx.x, ld);\n";
+        if (pack == 3) {
+            if (v.tail > 0) {
+                // pairs of tiles for blocks < G1, then one tile per block for the last S tiles
+                // (jit_grid below counts the same T_ / S_ / P_ / G1)
+                o << "  const uint32_t T_ = (B + 255u) / 256u, S_ = (uint32_t)(((uint64_t)T_ * " << v.tail
+                  << "u) / 100u);\n";
+                o << "  const uint32_t P_ = (T_ - S_) & ~1u, G1 = P_ / 2u;\n";
+                o << "  if (blockIdx.x >= G1) {\n";
+                o << "    const uint32_t t = P_ + (blockIdx.x - G1), b = t * 256u + threadIdx.x;\n";
+                o << "    if (b >= B) return;\n";
+                o << "    const int64_t o = (int64_t)t * bs;\n";
+                o << "    rbamd::dev::rnea_lane<T, N, " << F << ", Topo>" << lane_args << "    return;\n  }\n";
+            }
+            o << seq_prologue;
+            o << "  rbamd::dev::rnea_lane_seq2<T, N, " << F
+              << ", Topo>(kModel, q + oA, qd + oA, qdd + oA, tau + oA, offA, offB, twoB, ld);\n}\n";
+        } else {
+            o << lane_prologue;
+            if (rev && com && pack == 1)
+                o << "  rbamd::dev::rnea_lane_rev<T, N, " << F << ">";
+            else if (park > 0)
+                o << "  rbamd::dev::rnea_lane_park<T, N, " << F << ", " << park << ">";
+            else
+                o << "  rbamd::dev::rnea_lane<T, N, " << F << ", Topo>";
+            o << lane_args << "}\n";
+        }
     } else if (kind == JitKind::RneaFd) {
         // one configuration per lane; the launcher takes this kind only for mass-matrix models
-        o << head << "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ qdd, const T *__restrict__ tau_in, T *__restrict__ tau, "
-             "T *__restrict__ qdd_out, uint32_t B, int64_t ld, int64_t bs) {\n";
+        sig(fused_params);
         if (pack == 5) {
             o << "  rbamd::dev::idfd_split_block1<T, N, " << F << ">(kModel, q, qd, qdd, tau_in, tau, qdd_out, B, ld, bs);\n}\n";
         } else {
-            o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-            o << "  if (b >= B) return;\n";
-            o << "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
+            o << lane_prologue;
             o << "  rbamd::dev::idfd_lane<T, N, " << F
               << ">(kModel, q + o, qd + o, qdd + o, tau_in + o, tau + o, qdd_out + o, threadIdx.x, ld);\n}\n";
         }
     } else if (kind == JitKind::Fd) {
-        o << head << "rb_jit_kernel(const T *__restrict__ q, const T *__restrict__ qd, "
-             "const T *__restrict__ tau, T *__restrict__ qdd, uint32_t B, int64_t ld, int64_t bs) {\n";
+        sig(dyn_params("tau", "qdd"));
+        const char *lane_args = "(kModel, q + o, qd + o, tau + o, qdd + o, threadIdx.x, ld);\n}\n";
+        const char *pair_args = "(kModel, q + oA, qd + oA, tau + oA, qdd + oA, offA, offB, ld);\n}\n";
         if (fdh && pack == 5) {
             o << "  rbamd::dev::fdh_split_block1<T, N, " << F << ">(kModel, q, qd, tau, qdd, B, ld, bs);\n}\n";
         } else if (fdh && pack == 4) {
             o << "  rbamd::dev::fdh_split_block2<N, " << F << ">(kModel, q, qd, tau, qdd, B, ld, bs);\n}\n";
         } else if (fdh && pack == 2) {
-            o << pair_prologue;
-            o << "  rbamd::dev::fdh_lane2<N, " << F << ">(kModel, q + oA, qd + oA, tau + oA, qdd + oA, offA, offB, ld);\n}\n";
+            o << pair_prologue << "  rbamd::dev::fdh_lane2<N, " << F << ">" << pair_args;
         } else if (fdh) {
-            o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-            o << "  if (b >= B) return;\n";
-            o << "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
-            o << "  rbamd::dev::fdh_lane<T, N, " << F << ", Topo>(kModel, q + o, qd + o, tau + o, qdd + o, threadIdx.x, ld);\n}\n";
+            o << lane_prologue << "  rbamd::dev::fdh_lane<T, N, " << F << ", Topo>" << lane_args;
         } else if (pack == 3) {
-            o << seq_prologue;
-            o << "  rbamd::dev::aba_lane_seq2<T, N, " << F
+            o << seq_prologue << "  rbamd::dev::aba_lane_seq2<T, N, " << F
               << ", Topo>(kModel, q + oA, qd + oA, tau + oA, qdd + oA, offA, offB, twoB, ld);\n}\n";
         } else if (pack == 2) {
-            o << pair_prologue;
-            o << "  rbamd::dev::aba_lane2<N, " << F
-              << ", Topo>(kModel, q + oA, qd + oA, tau + oA, qdd + oA, offA, offB, ld);\n}\n";
+            o << pair_prologue << "  rbamd::dev::aba_lane2<N, " << F << ", Topo>" << pair_args;
         } else {
-            o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-            o << "  if (b >= B) return;\n";
-            o << "  const int64_t o = (int64_t)blockIdx.x * bs;\n";
-            o << "  rbamd::dev::aba_lane<T, N, " << F << ", Topo>(kModel, q + o, qd + o, tau + o, qdd + o, threadIdx.x, ld);\n}\n";
+            o << lane_prologue << "  rbamd::dev::aba_lane<T, N, " << F << ", Topo>" << lane_args;
         }
-    } else if (kind == JitKind::Rollout && pack == 4) {
-        o << head << "rb_jit_kernel(T *__restrict__ q, T *__restrict__ qd, const T *__restrict__ tau_seq, T dt, "
-             "int K, T *__restrict__ traj, uint32_t B, int64_t ld) {\n";
-        o << "  rbamd::dev::rollout_split_block2<N, " << F << ">(kModel, q, qd, tau_seq, dt, K, traj, B, ld);\n}\n";
-    } else if (kind == JitKind::Rollout && pack == 2) {
-        o << head << "rb_jit_kernel(T *__restrict__ q, T *__restrict__ qd, const T *__restrict__ tau_seq, T dt, "
-             "int K, T *__restrict__ traj, uint32_t B, int64_t ld) {\n";
-        o << "  __shared__ rbamd::dev::RolloutShared2<N> sh;\n";
-        o << "  const uint32_t bA = blockIdx.x * 512u + threadIdx.x;\n";
-        o << "  if (bA >= B) return;\n";
-        o << "  const uint32_t offA = bA * 4u, offB = bA + 256u < B ? offA + 1024u : offA;\n";
-        o << "  rbamd::dev::rollout_lane2<N, " << F << ", Topo>(kModel, q, qd, tau_seq, dt, K, traj, offA, offB, ld, sh);\n}\n";
     } else if (kind == JitKind::Rollout) {
-        o << head << "rb_jit_kernel(T *__restrict__ q, T *__restrict__ qd, const T *__restrict__ tau_seq, T dt, "
-             "int K, T *__restrict__ traj, uint32_t B, int64_t ld) {\n";
-        o << "  __shared__ rbamd::dev::RolloutShared<T, N> sh;\n";
-        o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-        o << "  if (b >= B) return;\n";
-        o << "  rbamd::dev::rollout_lane<T, N, " << F << ", Topo>(kModel, q, qd, tau_seq, dt, K, traj, b, ld, sh);\n}\n";
-    } else if (kind == JitKind::FwdKin || kind == JitKind::Jac) {
-        // q-only kernels take the block strides of their input and output rows (256 for SoA;
-        // n * 256 / rows * 256 for the tiled layout), as the lane kernels above
-        o << head << "rb_jit_kernel(const T *__restrict__ q, T *__restrict__ out, uint32_t B, int64_t ld, "
-             "int64_t bs_in, int64_t bs_out) {\n";
-        o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-        o << "  if (b >= B) return;\n";
-        o << "  rbamd::dev::" << (kind == JitKind::FwdKin ? "fwd_kin" : "jac") << "_lane_tree<T, N, " << F
-          << ", Topo>(kModel, q + (int64_t)blockIdx.x * bs_in, out + (int64_t)blockIdx.x * bs_out, threadIdx.x, ld);\n}\n";
-    } else {
-        o << head << "rb_jit_kernel(const T *__restrict__ q, T *__restrict__ H, uint32_t B, int64_t ld, "
-             "int64_t bs_in, int64_t bs_out) {\n";
-        o << "  const uint32_t b = blockIdx.x * 256u + threadIdx.x;\n";
-        o << "  if (b >= B) return;\n";
-        o << "  rbamd::dev::crba_lane<T, N, " << F
-          << ", Topo>(kModel, q + (int64_t)blockIdx.x * bs_in, H + (int64_t)blockIdx.x * bs_out, threadIdx.x, ld);\n}\n";
+        sig(rollout_params);
+        if (pack == 4) {
+            o << "  rbamd::dev::rollout_split_block2<N, " << F << ">(kModel, q, qd, tau_seq, dt, K, traj, B, ld);\n}\n";
+        } else if (pack == 2) {
+            o << "  __shared__ rbamd::dev::RolloutShared2<N> sh;\n";
+            o << "  const uint32_t bA = blockIdx.x * 512u + threadIdx.x;\n";
+            o << "  if (bA >= B) return;\n";
+            o << "  const uint32_t offA = bA * 4u, offB = bA + 256u < B ? offA + 1024u : offA;\n";
+            o << "  rbamd::dev::rollout_lane2<N, " << F << ", Topo>(kModel, q, qd, tau_seq, dt, K, traj, offA, offB, ld, sh);\n}\n";
+        } else {
+            o << "  __shared__ rbamd::dev::RolloutShared<T, N> sh;\n";
+            o << lane_guard;
+            o << "  rbamd::dev::rollout_lane<T, N, " << F << ", Topo>(kModel, q, qd, tau_seq, dt, K, traj, b, ld, sh);\n}\n";
+        }
+    } else {  // CRBA, fwd_kin, jac
+        const char *out = kind == JitKind::Crba ? "H" : "out";
+        const char *lane = kind == JitKind::Crba ? "crba_lane" : kind == JitKind::FwdKin ? "fwd_kin_lane_tree" : "jac_lane_tree";
+        sig(q_params(out));
+        o << lane_guard;
+        o << "  rbamd::dev::" << lane << "<T, N, " << F << ", Topo>(kModel, q + (int64_t)blockIdx.x * bs_in, " << out
+          << " + (int64_t)blockIdx.x * bs_out, threadIdx.x, ld);\n}\n";
     }
     std::string src = o.str();
     if (tab) {  // every kernel fills the block's sincos table first (all lanes still present)
@@ -473,6 +587,20 @@ std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pa
         if (body != std::string::npos) src.insert(body + 4, "  rbamd::dev::sctab_init();\n");
     }
     return src;
+}
+
+unsigned jit_grid(const JitKernel &jk, uint32_t B) {
+    const int pack = jk.variant.pack;
+    if (pack == 3 && jk.variant.tail > 0) {  // pairs, then a one-per-lane tail (jit_source's T_ / S_ / P_ / G1)
+        const unsigned T = (unsigned)(((uint64_t)B + 255u) / 256u);
+        const unsigned S = (unsigned)(((uint64_t)T * (unsigned)jk.variant.tail) / 100u);
+        const unsigned P = (T - S) & ~1u;
+        return P / 2u + (T - P);
+    }
+    // pack 2 / 3: two configurations per lane; pack 5: the one-per-lane wave split, 128 per block
+    // (pack 4, the packed split, covers 256 per block like one per lane)
+    const unsigned per_block = pack == 5 ? 128u : 256u * ((pack == 2 || pack == 3) ? 2u : 1u);
+    return (unsigned)(((uint64_t)B + per_block - 1) / per_block);
 }
 
 namespace {
@@ -516,20 +644,17 @@ bool rtc_compile(const std::string &src, const std::string &arch, bool no_licm, 
 }
 }  // namespace
 
-bool jit_compile(const Model &m, JitKind kind, bool f64, bool fast, const std::string &arch,
-                 std::vector<char> *code, std::string *error, int pack, int tail, int nt, std::string *final_src) {
-    std::string src = jit_source(m, kind, f64, fast, pack, tail, nt);
-    // The paired fp32 rollout and the fp64 rollout of short chains keep 2 waves/SIMD only
-    // without machine LICM: hoisting per-step address arithmetic and constants out of the K
-    // loop costs the VGPRs below 256 (fp64 FR3: 212 instead of 264).
-    const bool no_licm = kind == JitKind::Rollout && jit_rollout_no_hoist(f64, m.n, pack > 0 ? pack : jit_pack(kind, f64, m.n));
+bool jit_compile(const Model &m, const JitVariant &v, const std::string &arch, std::vector<char> *code,
+                 std::string *error, std::string *final_src) {
+    std::string src = jit_source(m, v, -1);
+    const bool no_licm = jit_no_licm(m, v);
     if (!rtc_compile(src, arch, no_licm, code, error)) return false;
     // Occupancy cliff (jit.hpp): no target asked for, none in the source, and the kernel just
     // past 256 registers -> rebuild with a 2-wave target; the first build stands if that fails.
     if (tuning().jit_waves < 0 && src.find("amdgpu_waves_per_eu") == std::string::npos) {
-        const int v = code_vgprs(*code);
-        if (v > 256 && v <= 272) {
-            std::string src2 = jit_source(m, kind, f64, fast, pack, tail, nt, 2), err2;
+        const int vgprs = code_vgprs(*code);
+        if (vgprs > 256 && vgprs <= 272) {
+            std::string src2 = jit_source(m, v, 2), err2;
             std::vector<char> code2;
             if (rtc_compile(src2, arch, no_licm, &code2, &err2)) {
                 code->swap(code2);
@@ -543,7 +668,7 @@ bool jit_compile(const Model &m, JitKind kind, bool f64, bool fast, const std::s
     if (const char *dir = std::getenv("RB_JIT_DUMP")) {
         static std::atomic<int> seq{0};
         const std::string base = std::string(dir) + "/jit_" + std::to_string(seq.fetch_add(1)) + "_k" +
-                                 std::to_string((int)kind) + (f64 ? "_f64" : "_f32") + "_p" + std::to_string(pack);
+                                 std::to_string((int)v.kind) + (v.f64 ? "_f64" : "_f32") + "_p" + std::to_string(v.pack);
         if (FILE *f = std::fopen((base + ".hip").c_str(), "wb")) {
             std::fwrite(src.data(), 1, src.size(), f);
             std::fclose(f);
@@ -556,10 +681,9 @@ bool jit_compile(const Model &m, JitKind kind, bool f64, bool fast, const std::s
     return true;
 }
 
-JitKernel jit_build(const Model &m, JitKind kind, bool f64, bool fast, int pack, int tail, int nt) {
+JitKernel jit_build(const Model &m, const JitVariant &v) {
     JitKernel jk;
-    jk.pack = jit_model_pack(m, kind, f64, pack);
-    if (kind == JitKind::Rnea && jk.pack == 3) jk.seq_tail = tail > 0 ? tail : 0;
+    jk.variant = v;
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
@@ -567,7 +691,7 @@ JitKernel jit_build(const Model &m, JitKind kind, bool f64, bool fast, int pack,
         return jk;
     }
     std::vector<char> code;
-    if (!jit_compile(m, kind, f64, fast, prop.gcnArchName, &code, &jk.error, jk.pack, jk.seq_tail, nt)) return jk;
+    if (!jit_compile(m, v, prop.gcnArchName, &code, &jk.error)) return jk;
     hipError_t e = hipModuleLoadData(&jk.module, code.data());
     if (e != hipSuccess) {
         jk.error = std::string("hipModuleLoadData: ") + hipGetErrorString(e);

@@ -30,46 +30,55 @@ namespace rbamd {
 enum class JitKind : int { Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6 };
 constexpr int kJitKinds = 7;
 
+// One compiled kernel of a model: with the model and the tuning knobs (jit_key), everything its
+// source and compile flags depend on.  jit_resolve is the only producer.
+struct JitVariant {
+    JitKind kind = JitKind::Rnea;
+    bool f64 = false;
+    bool fast = false;  // fp32 hardware sin / cos (v_sin_f32 / v_cos_f32); never set for fp64
+    // the configurations-per-lane form the kernel really has: 1 one per lane, 2 paired fp32 lanes
+    // (512 per block), 3 sequential pair, 4 / 5 the packed / one-per-lane wave split
+    int pack = 1;
+    int tail = 0;  // sequential-pair RNEA only: percent of the launch's tiles run one per lane (0 none)
+    int nt = -1;   // the non-temporal load / store bits compiled in (RB_NT); -1 = the kind's tuning
+};
+
 struct JitKernel {
     hipModule_t module = nullptr;
     hipFunction_t function = nullptr;  // the lane kernel (any layout)
-    int pack = 1;                      // configurations per lane (2: paired fp32 lanes, 512 per block)
-    int seq_tail = 0;                  // pack 3: trailing tiles run one per lane (tuning seq_tail)
+    JitVariant variant;                // what was built; jit_grid reads its pack and tail
     unsigned block = 256;              // threads per block
     std::string error;                 // non-empty when compilation failed
 };
 
 bool jit_enabled();
 
+// The kernel variant a launch of B configurations of `kind` takes on this model (tiled: the
+// [ceil(B/256)][n][256] layout): every batch-, layout- and model-dependent choice of lane form,
+// tail, load / store policy and trig form is made here.  fast_trig: the process's fp32 trig
+// flag (RB_FAST_TRIG).
+JitVariant jit_resolve(const Model &m, JitKind kind, bool f64, uint32_t B, bool tiled, bool fast_trig);
+
+// Cache key of a variant's kernel: the variant and every tuning value that changes the source
+// or the compile flags (tuning.hpp).
+std::string jit_key(const Model &m, const JitVariant &v);
+
 // Generated HIP source for one specialised kernel (exposed for tests / inspection).
-// pack: configurations per lane, 0 = the jit_pack policy.
-// tail: sequential-pair RNEA only -- percent of the launch's tiles run one per lane (0 none).
-// nt: the non-temporal load / store bits compiled in (RB_NT); -1 = jit_nt(kind).
-// waves: amdgpu_waves_per_eu target of the kernel; -1 = the policy (jit_waves and the per-form
-// rules in jit_source).  jit_compile may rebuild with a 2-wave target (occupancy cliff, below).
-std::string jit_source(const Model &m, JitKind kind, bool f64, bool fast, int pack = 0, int tail = 0, int nt = -1,
-                       int waves = -1);
+// waves: amdgpu_waves_per_eu target of the kernel; -1 = the policy (the jit_waves tuning and the
+// per-form rules in jit_source).  jit_compile may rebuild with a 2-wave target (occupancy cliff,
+// below).
+std::string jit_source(const Model &m, const JitVariant &v, int waves);
+
+// Blocks of a launch of B configurations on `jk` (the grid its source was written for).
+unsigned jit_grid(const JitKernel &jk, uint32_t B);
 
 // Unified VGPR count (arch VGPRs + AGPRs) of a code object's kernel, from its AMDGPU metadata;
 // -1 if not found.
 int code_vgprs(const std::vector<char> &code);
 
-// Non-temporal access bits of `kind`'s JIT source, and the cache-key suffix of every
-// tuning value that changes the source (tuning.hpp).
-int jit_nt(JitKind kind);
-bool jit_opaque(JitKind kind, bool f64, int n);
-int jit_waves(JitKind kind, bool f64, int n);
-// Configurations per lane of `kind`'s lane kernel (tuning `pack`): 2 = paired fp32 lanes.
-int jit_pack(JitKind kind, bool f64, int n);
-std::string jit_tag(JitKind kind, bool f64, int n);
 // Forward-dynamics algorithm for this model (tuning fd_form): 2 = mass-matrix method
 // (fdh_body.hip.hpp), 1 = Articulated-Body Algorithm (aba_body.hip.hpp).
 int jit_fd_form(const Model &m, JitKind kind = JitKind::Fd);
-// The lane form a kernel of this model really takes for the requested pack (0 = policy).
-int jit_model_pack(const Model &m, JitKind kind, bool f64, int pack_req);
-// Percent of a sequential-pair RNEA launch's tiles run one per lane for this layout (tuning
-// seq_tail; auto: 75 for the tiled layout, 0 for SoA).
-int jit_seq_tail(bool tiled);
 
 // hipRTC compilation only (no device needed): fills `code` with the code object.  Occupancy
 // cliff: a kernel built without an occupancy target that lands just past 256 registers (one
@@ -79,11 +88,10 @@ int jit_seq_tail(bool tiled);
 // preloaded, tuning.hpp kernarg_preload).
 // final_src (optional): the source of the code object returned -- the occupancy-cliff rebuild's
 // when that rule applied (multibody_jit_source_ex reports this one).
-bool jit_compile(const Model &m, JitKind kind, bool f64, bool fast, const std::string &arch,
-                 std::vector<char> *code, std::string *error, int pack = 0, int tail = 0,
-                 int nt = -1, std::string *final_src = nullptr);
+bool jit_compile(const Model &m, const JitVariant &v, const std::string &arch, std::vector<char> *code,
+                 std::string *error, std::string *final_src = nullptr);
 
 // Compiles and loads the kernel on the current device.  Never throws.
-JitKernel jit_build(const Model &m, JitKind kind, bool f64, bool fast, int pack = 0, int tail = 0, int nt = -1);
+JitKernel jit_build(const Model &m, const JitVariant &v);
 
 }  // namespace rbamd

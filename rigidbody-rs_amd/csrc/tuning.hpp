@@ -20,8 +20,8 @@ struct Tuning {
     // fp32 (spatial.hip.hpp f2; 512 configurations per 256-lane block), 1 = one per lane,
     // 4 = bias / mass-matrix split over a pair of packed waves, 5 = that split one per lane;
     // RNEA: 3 = two configurations per lane one after the other, 1 = one per lane;
-    // -1 auto (capi.cpp jit_rnea / jit_fd / launch_rollout_any by batch size and layout,
-    // jit.cpp jit_pack).
+    // -1 auto (jit.cpp jit_resolve: rnea_pack / fd_pack / rollout_pack / idfd_pack by batch size
+    // and layout, jit_pack).
     std::atomic<int> pack{-1};
     // Precompiled (generic) RNEA launch form: 1 grid-stride + register prefetch, 0 one
     // configuration per lane, -1 auto (streaming for fp64 and chains longer than 8 links,
@@ -56,7 +56,7 @@ struct Tuning {
     // fp32 3.46 vs 3.89); -1 auto = 3, except 0 for the fp32 RNEA of chains up to 8 links at
     // batches >= 2^19 on the tiled layout (FR3 2^20: 22.4 vs 25.2 us, steady where nt=3 swings
     // 20-25; SoA rows keep 3: 24.3 vs 24.9; the 30-link chain 99.9 vs 91.3 and the 14-DOF tree
-    // 44.2 vs 41.2 keep 3) -- capi.cpp jit_rnea.
+    // 44.2 vs 41.2 keep 3) -- jit.cpp jit_resolve.
     std::atomic<int> rnea_nt{-1};
     // JIT forward dynamics / rollout: same bits as rnea_nt (-5% fp32 FD kernel time).
     std::atomic<int> fd_nt{3};

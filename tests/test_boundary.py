@@ -287,7 +287,7 @@ def test_jit_kernel_forms_compile(ffi, fr3_text):
     assert mb.jit_compile(f64=False, kind="rollout") > 1000
     assert "sctab_init" in mb.jit_source(True, "rnea") and "sctab_init" not in mb.jit_source(False, "rnea")
     # the source of the kernel a given launch takes (multibody_jit_source_ex): the auto policy's
-    # form, tail and load / store policy per batch size and layout (capi.cpp jit_shape)
+    # form, tail and load / store policy per batch size and layout (jit.cpp jit_resolve)
     head = mb.jit_source(True, "rnea", batch=1 << 20, tiled=True)
     assert "rnea_lane_seq2<" in head and "rnea_lane<" in head and "S_ =" in head  # pairs + one-per-lane tail
     assert "rnea_lane_seq2<" in mb.jit_source(False, "rnea", batch=1 << 20, tiled=True)
