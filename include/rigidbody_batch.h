@@ -21,6 +21,10 @@
  *   multibody_crba_batch_*     <- multibody_crba      (lib.rs:32-43)
  *   multibody_fwd_kin_batch_*  <- multibody_fwd_kin   (lib.rs:46-57)
  *   multibody_jac_batch_*      <- multibody_jac       (lib.rs:60-70)
+ *   multibody_rnea_deriv_batch_* / multibody_fd_deriv_batch_*
+ *                              <- no reference entry point: the analytical derivatives of the
+ *                                 two dynamics above with respect to q, qd (and tau), for
+ *                                 trajectory optimisation ("Analytical derivatives" below)
  *
  * Layout: structure of arrays.  Joint j of configuration b lives at x[j * ld + b]
  * (ld >= batch, the leading dimension).  Matrix outputs store element e of each
@@ -147,7 +151,10 @@ int multibody_upload(const Multibody *mb);
 
 /* Which kernel a launch of `batch` configurations (tiled != 0: the *_tiled entry points)
  * runs for this model on the current device; kind 0 = rnea, 1 = fd, 2 = crba, 3 = rollout,
- * 4 = fwd_kin, 5 = jac, 6 = rnea_fd (multibody_rnea_fd_batch_*).  1 = model-specialised kernel
+ * 4 = fwd_kin, 5 = jac, 6 = rnea_fd (multibody_rnea_fd_batch_*), 7 = rnea_deriv, 8 = fd_deriv
+ * (multibody_rnea_deriv_batch_* / multibody_fd_deriv_batch_*; for a model outside their scope
+ * these queries return -RB_ERR_UNSUPPORTED and multibody_jit_source_ex the empty source; they
+ * have no generic kernel, 0 means their calls fail).  1 = model-specialised kernel
  * compiled at first use by hipRTC (this call compiles exactly the form such a launch takes), 0 =
  * precompiled generic kernel (also when hipRTC failed; rb_last_error() holds the log -- a tree
  * model's calls then fail with RB_ERR_UNSUPPORTED; kind 6: the model has no fused kernel and
@@ -291,6 +298,73 @@ int multibody_fwd_kin_batch_tiled_f64(const Multibody *mb, const double *q, doub
                                       void *stream);
 int multibody_jac_batch_tiled_f32(const Multibody *mb, const float *q, float *J, int64_t batch, void *stream);
 int multibody_jac_batch_tiled_f64(const Multibody *mb, const double *q, double *J, int64_t batch, void *stream);
+
+/* ---- analytical derivatives of the inverse and forward dynamics ----------------- */
+/* For a configuration (q, qd, qdd) of an n-DOF model, tau = rnea(q, qd, qdd):
+ *   dtau_dq [i, k] = d tau_i / d q_k        dtau_dqd[i, k] = d tau_i / d qd_k
+ * (d tau / d qdd is sym(H): multibody_crba_batch_*).  For (q, qd, tau), qdd = fd(q, qd, tau) as
+ * multibody_fd_batch_* defines it:
+ *   dqdd_dq   = -sym(H)^-1 dtau_dq (q, qd, qdd)
+ *   dqdd_dqd  = -sym(H)^-1 dtau_dqd(q, qd, qdd)
+ *   dqdd_dtau =  sym(H)^-1                       (full symmetric, both triangles written)
+ * Layout: the matrix convention above, element e = i + n k (row i the output index, column k the
+ * differentiated joint, column-major) of configuration b at out[e * ld + b]; each matrix is
+ * [n * n][ld].  Any output may be NULL and is then neither computed nor stored; every output
+ * NULL is RB_ERR_NULL.  qdd_out equals multibody_fd_batch_* bit for bit (the same lane
+ * arithmetic).  An output that is also an input, or passed twice, is refused (RB_ERR_ARG).
+ * batch >= 0, split at 2^28 per launch; ld >= batch.
+ *
+ * Scope: serial revolute chains (z-axis or RB_MODEL_GENERAL_AXES) of any supported length for
+ * rnea_deriv (chains past 16 links run rolled loops over per-lane arrays: correct, not tuned);
+ * fd_deriv on the mass-matrix forward dynamics only (chains up to 12 links).  Kinematic trees,
+ * prismatic joints, a floating base, and fd_deriv on longer chains return RB_ERR_UNSUPPORTED;
+ * rb_last_error() names the condition.  The batched forms run on model-specialised (hipRTC)
+ * kernels only (kinds 7 and 8): with hipRTC disabled or failed they return RB_ERR_UNSUPPORTED
+ * with the log.  SoA rows only (no tiled form).
+ *
+ * Algorithm (rnea_deriv_body.hip.hpp): forward-mode sweeps of the RNEA recursion, one
+ * differentiated joint at a time, each column stored as it completes; fd_deriv evaluates the
+ * bias, H and L D L^T once and back-substitutes every column through the kept factors.
+ *
+ * Input domain: as above -- a configuration with a NaN / Inf input or an angle past the bound gets
+ * NaN in every element of every output; the others are unaffected.
+ *
+ * Accuracy (tests/test_deriv_host.py, tests/test_gpu_deriv.py; reference: Richardson-extrapolated
+ * central differences of the fp64 oracle, self-consistent to 1e-10).  fp64: dtau_dq, dtau_dqd
+ * |d| <= 1e-8 (1 + |ref|) element-wise; the forward-dynamics matrices satisfy
+ * sym(H) dqdd_dtau = I to 1e-9 and sym(H) dqdd_dq + dtau_dq = 0 to 1e-8, scaled.  fp32 (FR3, over
+ * its limits, measured): dtau_dq, dtau_dqd per column max_i |d_ik| <= 1e-4 (1 + max_i |ref_ik|)
+ * (measured 2.2e-6); the forward-dynamics matrices X as row-sum residuals
+ * |H_s X + dtau_dq| <= 60 eps32 (|H_s| |X| + |dtau_dq|) (measured constant 14.8, below the 24 of the
+ * fp32 forward-dynamics contract above). */
+int multibody_rnea_deriv_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                   float *dtau_dq, float *dtau_dqd, int64_t batch, int64_t ld, void *stream);
+int multibody_rnea_deriv_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                   double *dtau_dq, double *dtau_dqd, int64_t batch, int64_t ld, void *stream);
+int multibody_fd_deriv_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau, float *qdd_out,
+                                 float *dqdd_dq, float *dqdd_dqd, float *dqdd_dtau, int64_t batch, int64_t ld,
+                                 void *stream);
+int multibody_fd_deriv_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                 double *qdd_out, double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau, int64_t batch,
+                                 int64_t ld, void *stream);
+/* Blocking host-pointer forms: [n][batch] inputs, [n * n][batch] matrices ([n][batch] qdd_out). */
+int multibody_rnea_deriv_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                        float *dtau_dq, float *dtau_dqd, int64_t batch);
+int multibody_rnea_deriv_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                        double *dtau_dq, double *dtau_dqd, int64_t batch);
+int multibody_fd_deriv_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                      float *qdd_out, float *dqdd_dq, float *dqdd_dqd, float *dqdd_dtau,
+                                      int64_t batch);
+int multibody_fd_deriv_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                      double *qdd_out, double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau,
+                                      int64_t batch);
+/* One configuration, fp64, caller-provided buffers (n * n doubles per matrix, n for qdd), on the
+ * calling thread: the same lane body compiled for the host, no GPU needed (an FMA3 / AVX2 CPU
+ * and a chain length of multibody_supported_dofs, else RB_ERR_UNSUPPORTED). */
+int multibody_rnea_deriv(const Multibody *mb, const double *q, const double *qd, const double *qdd, double *dtau_dq,
+                         double *dtau_dqd);
+int multibody_fd_deriv(const Multibody *mb, const double *q, const double *qd, const double *tau, double *qdd,
+                       double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau);
 
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,

@@ -35,7 +35,7 @@
 
 #define RB_VERSION "rigidbody-rs_amd 0.2.0 (gfx950)"
 
-static const char *const kKindMsg = "kind must be 0 rnea, 1 fd, 2 crba, 3 rollout, 4 fwd_kin, 5 jac or 6 rnea_fd";
+static const char *const kKindMsg = "kind must be 0 rnea, 1 fd, 2 crba, 3 rollout, 4 fwd_kin, 5 jac, 6 rnea_fd, 7 rnea_deriv or 8 fd_deriv";
 
 namespace {
 
@@ -215,8 +215,8 @@ const rbamd::JitKernel *jit_get(const Multibody *mb, const rbamd::JitVariant &v)
 
 // A tree / prismatic model has no precompiled kernel: without its hipRTC kernel the launch
 // is refused (hipErrorNotSupported, reported as RB_ERR_UNSUPPORTED with the reason).
-hipError_t no_generic(const Multibody *mb) {
-    std::string why = "kinematic-tree / prismatic models run only on model-specialised (hipRTC) kernels";
+hipError_t no_generic(const Multibody *mb, const char *what = "kinematic-tree / prismatic models run") {
+    std::string why = std::string(what) + " only on model-specialised (hipRTC) kernels";
     if (!rbamd::jit_enabled()) {
         why += ", which are disabled (RB_JIT=0 / rb_set_tuning(\"jit\", 0))";
     } else {
@@ -355,6 +355,32 @@ hipError_t launch_kin_any(const Multibody *mb, bool jac, const T *mdl, const T *
     const int64_t n = mb->model.n;
     TileStrides st = tile_strides(tiled, ld, n, jac ? 6 * n : 3);
     void *args[] = {(void *)&q, (void *)&out, (void *)&B, (void *)&st.lda, (void *)&st.bs_in, (void *)&st.bs_out};
+    return jit_launch(jk, B, args, s);
+}
+
+// Analytical derivatives (rnea_deriv_body.hip.hpp): model-specialised kernels only, SoA rows; a
+// NULL output is neither evaluated nor stored.  Without the kernel (hipRTC off or failed) the
+// launch is refused as a tree model's is.
+template <typename T>
+hipError_t launch_rnea_deriv(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *dq, T *dqd, uint32_t B,
+                             int64_t ld, hipStream_t s) {
+    if (B == 0) return hipSuccess;
+    const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::RneaDeriv, sizeof(T) == 8, B, false);
+    if (!jk) return no_generic(mb, "the dynamics derivatives run");
+    int64_t bs = 256;
+    void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&dq, (void *)&dqd, (void *)&B, (void *)&ld, (void *)&bs};
+    return jit_launch(jk, B, args, s);
+}
+
+template <typename T>
+hipError_t launch_fd_deriv(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, T *dq, T *dqd, T *dtau,
+                           uint32_t B, int64_t ld, hipStream_t s) {
+    if (B == 0) return hipSuccess;
+    const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::FdDeriv, sizeof(T) == 8, B, false);
+    if (!jk) return no_generic(mb, "the dynamics derivatives run");
+    int64_t bs = 256;
+    void *args[] = {(void *)&q,   (void *)&qd,   (void *)&tau, (void *)&qdd, (void *)&dq,
+                    (void *)&dqd, (void *)&dtau, (void *)&B,   (void *)&ld,  (void *)&bs};
     return jit_launch(jk, B, args, s);
 }
 
@@ -543,6 +569,56 @@ int idfd_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, const
     });
 }
 
+// RB_ERR_UNSUPPORTED (with the condition that failed) when `kind` has no kernel for this model.
+int deriv_supported(const Multibody *mb, rbamd::JitKind kind) {
+    const std::string why = rbamd::jit_kind_unsupported(mb->model, kind);
+    return why.empty() ? (int)RB_OK : set_err(RB_ERR_UNSUPPORTED, why);
+}
+
+// The derivative entry points' own argument checks: inputs present, at least one output, no
+// output that is also an input or another output, a model in scope.
+template <typename T>
+int deriv_args_ok(const Multibody *mb, rbamd::JitKind kind, const char *name, std::initializer_list<const T *> in,
+                  std::initializer_list<const T *> out) {
+    for (const T *p : in)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    bool any = false;
+    for (const T *o : out) any = any || o != nullptr;
+    if (!any) return set_err(RB_ERR_NULL, std::string(name) + ": every output is NULL");
+    for (const T *const *o = out.begin(); o != out.end(); ++o) {
+        if (!*o) continue;
+        for (const T *i : in)
+            if (*o == i) return set_err(RB_ERR_ARG, std::string(name) + ": an output array is also an input");
+        for (const T *const *o2 = out.begin(); o2 != o; ++o2)
+            if (*o == *o2) return set_err(RB_ERR_ARG, std::string(name) + ": two outputs are the same array");
+    }
+    return deriv_supported(mb, kind);
+}
+
+template <typename T>
+int rnea_deriv_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *dq, T *dqd, int64_t batch,
+                     int64_t ld, void *stream) {
+    auto args_ok = [&] {
+        return deriv_args_ok<T>(mb, rbamd::JitKind::RneaDeriv, "rnea_deriv", {q, qd, qdd}, {dq, dqd});
+    };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "rnea_deriv launch", [&](const T *, int64_t b0, uint32_t nb) {
+        return launch_rnea_deriv<T>(mb, q + b0, qd + b0, qdd + b0, dq ? dq + b0 : nullptr, dqd ? dqd + b0 : nullptr, nb,
+                                    ld, (hipStream_t)stream);
+    });
+}
+
+template <typename T>
+int fd_deriv_batch(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, T *dq, T *dqd, T *dtau,
+                   int64_t batch, int64_t ld, void *stream) {
+    auto args_ok = [&] {
+        return deriv_args_ok<T>(mb, rbamd::JitKind::FdDeriv, "fd_deriv", {q, qd, tau}, {qdd, dq, dqd, dtau});
+    };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "fd_deriv launch", [&](const T *, int64_t b0, uint32_t nb) {
+        return launch_fd_deriv<T>(mb, q + b0, qd + b0, tau + b0, qdd ? qdd + b0 : nullptr, dq ? dq + b0 : nullptr,
+                                  dqd ? dqd + b0 : nullptr, dtau ? dtau + b0 : nullptr, nb, ld, (hipStream_t)stream);
+    });
+}
+
 template <typename T>
 int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt, int K, T *traj, int64_t batch,
                   int64_t ld, void *stream) {
@@ -653,6 +729,79 @@ int idfd_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, const 
         const size_t per = (size_t)mb->model.n * (size_t)batch;
         return idfd_batch<T>(mb, d, d + per, d + 2 * per, d + 3 * per, o, o + per, batch, batch, s);
     });
+}
+
+// The derivative entry points' blocking host form: nin [n][batch] inputs; outputs of rows[k] rows
+// each ([rows][batch]), a NULL one skipped.  check() runs after the handle / batch checks and
+// before any device work; launch(d_in, d_out[], stream) gets the device arrays (NULL for a skipped
+// output).
+template <typename T, int NOUT, typename Check, typename Launch>
+int host_deriv_batch(const Multibody *mb, const T *const *in, int nin, T *const *out, const int64_t *rows, int64_t batch,
+                     Check check, Launch launch) {
+    int rc = check_batch(mb, batch, batch);
+    if (rc) return rc;
+    if (batch == 0) return RB_OK;
+    if ((rc = check())) return rc;
+    const size_t per = (size_t)mb->model.n * (size_t)batch;
+    size_t total = per * nin;
+    size_t at[NOUT];
+    for (int k = 0; k < NOUT; ++k) {
+        at[k] = total;
+        if (out[k]) total += (size_t)rows[k] * (size_t)batch;
+    }
+    T *d = nullptr;
+    hipStream_t s = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e != hipSuccess) return hip_err(e, "hipStreamCreate");
+    e = hipMallocAsync((void **)&d, total * sizeof(T), s);
+    if (e != hipSuccess) { (void)hipStreamDestroy(s); return hip_err(e, "hipMallocAsync"); }
+    for (int k = 0; k < nin && e == hipSuccess; ++k)
+        e = hipMemcpyAsync(d + k * per, in[k], per * sizeof(T), hipMemcpyHostToDevice, s);
+    T *dout[NOUT];
+    for (int k = 0; k < NOUT; ++k) dout[k] = out[k] ? d + at[k] : nullptr;
+    if (e == hipSuccess) rc = launch(d, dout, s);
+    else rc = hip_err(e, "hipMemcpyAsync H2D");
+    for (int k = 0; k < NOUT && rc == RB_OK; ++k) {
+        if (!out[k]) continue;
+        e = hipMemcpyAsync(out[k], dout[k], (size_t)rows[k] * (size_t)batch * sizeof(T), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) rc = hip_err(e, "hipMemcpyAsync D2H");
+    }
+    (void)hipFreeAsync(d, s);
+    e = hipStreamSynchronize(s);
+    if (rc == RB_OK && e != hipSuccess) rc = hip_err(e, "hipStreamSynchronize");
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+template <typename T>
+int rnea_deriv_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *dq, T *dqd, int64_t batch) {
+    const T *in[3] = {q, qd, qdd};
+    T *out[2] = {dq, dqd};
+    const int64_t nn = mb ? (int64_t)mb->model.n * mb->model.n : 0;
+    const int64_t rows[2] = {nn, nn};
+    return host_deriv_batch<T, 2>(
+        mb, in, 3, out, rows, batch,
+        [&] { return deriv_args_ok<T>(mb, rbamd::JitKind::RneaDeriv, "rnea_deriv", {q, qd, qdd}, {dq, dqd}); },
+        [&](T *d, T *const *o, hipStream_t s) {
+            const size_t per = (size_t)mb->model.n * (size_t)batch;
+            return rnea_deriv_batch<T>(mb, d, d + per, d + 2 * per, o[0], o[1], batch, batch, s);
+        });
+}
+
+template <typename T>
+int fd_deriv_host(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, T *dq, T *dqd, T *dtau,
+                  int64_t batch) {
+    const T *in[3] = {q, qd, tau};
+    T *out[4] = {qdd, dq, dqd, dtau};
+    const int64_t n = mb ? mb->model.n : 0;
+    const int64_t rows[4] = {n, n * n, n * n, n * n};
+    return host_deriv_batch<T, 4>(
+        mb, in, 3, out, rows, batch,
+        [&] { return deriv_args_ok<T>(mb, rbamd::JitKind::FdDeriv, "fd_deriv", {q, qd, tau}, {qdd, dq, dqd, dtau}); },
+        [&](T *d, T *const *o, hipStream_t s) {
+            const size_t per = (size_t)mb->model.n * (size_t)batch;
+            return fd_deriv_batch<T>(mb, d, d + per, d + 2 * per, o[0], o[1], o[2], o[3], batch, batch, s);
+        });
 }
 }  // namespace
 
@@ -840,7 +989,8 @@ int check_kernel_query(const Multibody *mb, int kind, int64_t batch) {
     if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
     if (kind < 0 || kind >= rbamd::kJitKinds) return set_err(RB_ERR_ARG, kKindMsg);
     if (batch < 1) return set_err(RB_ERR_ARG, "batch must be positive");
-    return RB_OK;
+    // a kind that has no kernel for this model (the derivative kinds outside their scope)
+    return deriv_supported(mb, (rbamd::JitKind)kind);
 }
 
 // The hipRTC source of the kernel a launch of `batch` configurations (tiled or SoA) would run:
@@ -853,6 +1003,7 @@ std::string shaped_source(const Multibody *mb, int kind, bool f64, int64_t batch
     // the length query and the copy of multibody_jit_source_ex come in pairs: one compile for both
     thread_local std::string t_key, t_src;
     const std::string plain = rbamd::jit_source(mb->model, v, -1);
+    if (plain.empty()) return plain;  // no such kernel for this model
     const std::string key = std::to_string((uintptr_t)mb) + ":" + std::to_string(rbamd::tuning_generation()) + ":" + plain;
     if (key == t_key) return t_src;
     std::vector<char> code;
@@ -901,8 +1052,10 @@ int multibody_jit_source(const Multibody *mb, int kind, int f64, char *buf, int6
 }
 
 int multibody_jit_source_ex(const Multibody *mb, int kind, int f64, int64_t batch, int tiled, char *buf, int64_t cap) {
-    if (int rc = check_kernel_query(mb, kind, batch)) return -rc;
-    const std::string src = shaped_source(mb, kind, f64 != 0, batch, tiled != 0);
+    int rc = check_kernel_query(mb, kind, batch);
+    if (rc && rc != RB_ERR_UNSUPPORTED) return -rc;
+    // a kind with no kernel for this model: the empty source
+    const std::string src = rc ? std::string() : shaped_source(mb, kind, f64 != 0, batch, tiled != 0);
     if (buf && cap > 0) {
         const size_t n = src.size() < (size_t)(cap - 1) ? src.size() : (size_t)(cap - 1);
         std::memcpy(buf, src.data(), n);
@@ -1083,6 +1236,69 @@ int multibody_fwd_kin_batch_f32(const Multibody *mb, const float *q, float *pos,
 int multibody_jac_batch_f32(const Multibody *mb, const float *q, float *J, int64_t batch, int64_t ld,
                             void *stream) {
     return kin_batch<float>(mb, true, q, J, batch, ld, stream);
+}
+
+// ------------------------------------------------------------- analytical derivatives
+int multibody_rnea_deriv_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                   float *dtau_dq, float *dtau_dqd, int64_t batch, int64_t ld, void *stream) {
+    return rnea_deriv_batch<float>(mb, q, qd, qdd, dtau_dq, dtau_dqd, batch, ld, stream);
+}
+int multibody_rnea_deriv_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                   double *dtau_dq, double *dtau_dqd, int64_t batch, int64_t ld, void *stream) {
+    return rnea_deriv_batch<double>(mb, q, qd, qdd, dtau_dq, dtau_dqd, batch, ld, stream);
+}
+int multibody_fd_deriv_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau, float *qdd_out,
+                                 float *dqdd_dq, float *dqdd_dqd, float *dqdd_dtau, int64_t batch, int64_t ld,
+                                 void *stream) {
+    return fd_deriv_batch<float>(mb, q, qd, tau, qdd_out, dqdd_dq, dqdd_dqd, dqdd_dtau, batch, ld, stream);
+}
+int multibody_fd_deriv_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                 double *qdd_out, double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau, int64_t batch,
+                                 int64_t ld, void *stream) {
+    return fd_deriv_batch<double>(mb, q, qd, tau, qdd_out, dqdd_dq, dqdd_dqd, dqdd_dtau, batch, ld, stream);
+}
+int multibody_rnea_deriv_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                        float *dtau_dq, float *dtau_dqd, int64_t batch) {
+    return rnea_deriv_host<float>(mb, q, qd, qdd, dtau_dq, dtau_dqd, batch);
+}
+int multibody_rnea_deriv_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                        double *dtau_dq, double *dtau_dqd, int64_t batch) {
+    return rnea_deriv_host<double>(mb, q, qd, qdd, dtau_dq, dtau_dqd, batch);
+}
+int multibody_fd_deriv_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                      float *qdd_out, float *dqdd_dq, float *dqdd_dqd, float *dqdd_dtau,
+                                      int64_t batch) {
+    return fd_deriv_host<float>(mb, q, qd, tau, qdd_out, dqdd_dq, dqdd_dqd, dqdd_dtau, batch);
+}
+int multibody_fd_deriv_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                      double *qdd_out, double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau,
+                                      int64_t batch) {
+    return fd_deriv_host<double>(mb, q, qd, tau, qdd_out, dqdd_dq, dqdd_dqd, dqdd_dtau, batch);
+}
+
+// Single configuration, fp64, on the calling thread: the lane body compiled for the host
+// (host_eval.cpp); no GPU involved.
+int multibody_rnea_deriv(const Multibody *mb, const double *q, const double *qd, const double *qdd, double *dtau_dq,
+                         double *dtau_dqd) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = deriv_args_ok<double>(mb, rbamd::JitKind::RneaDeriv, "rnea_deriv", {q, qd, qdd}, {dtau_dq, dtau_dqd}))
+        return rc;
+    if (!rbamd::host_rnea_deriv(mb->model, mb->pk64.data(), q, qd, qdd, dtau_dq, dtau_dqd))
+        return set_err(RB_ERR_UNSUPPORTED, "rnea_deriv: the single-configuration form runs on the host and needs an "
+                                           "FMA3 / AVX2 CPU");
+    return RB_OK;
+}
+
+int multibody_fd_deriv(const Multibody *mb, const double *q, const double *qd, const double *tau, double *qdd,
+                       double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = deriv_args_ok<double>(mb, rbamd::JitKind::FdDeriv, "fd_deriv", {q, qd, tau},
+                                       {qdd, dqdd_dq, dqdd_dqd, dqdd_dtau}))
+        return rc;
+    if (!rbamd::host_fd_deriv(mb->model, mb->pk64.data(), q, qd, tau, qdd, dqdd_dq, dqdd_dqd, dqdd_dtau))
+        return set_err(RB_ERR_UNSUPPORTED, "fd_deriv: the single-configuration form runs on the host and needs an "
+                                           "FMA3 / AVX2 CPU");
+    return RB_OK;
 }
 
 // ------------------------------------------------------------- batched (host)

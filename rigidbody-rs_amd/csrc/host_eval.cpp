@@ -13,6 +13,7 @@
 // (the recursion is written in fused multiply-adds); without it the GPU path serves.
 #include "host_eval.hpp"
 
+#include "rnea_deriv_body.hip.hpp"  // first: it declares the host reciprocal fdh_body's L D L^T takes
 #include "crba_body.hip.hpp"
 #include "dofs.hpp"
 #include "kernels.hpp"
@@ -101,6 +102,65 @@ RB_HOST_FMA bool jac_fma(int n, const double *mdl, const double *q, double *J) {
     }
 }
 
+RB_HOST_FMA bool rnea_deriv_fma(int n, const double *mdl, const double *q, const double *qd, const double *qdd,
+                                double *dq, double *dqd) {
+    switch (n) {
+#define X(N)                                                                                        \
+    case N: {                                                                                       \
+        double a[N], b[N], c[N];                                                                    \
+        for (int j = 0; j < N; ++j) {                                                               \
+            a[j] = q[j];                                                                            \
+            b[j] = qd[j];                                                                           \
+            c[j] = qdd[j];                                                                          \
+        }                                                                                           \
+        dev::rnea_deriv_eval<double, N, false>(                                                     \
+            mdl, a, b, c, dq != nullptr, dqd != nullptr, [&](int e, double v) { dq[e] = v; },       \
+            [&](int e, double v) { dqd[e] = v; });                                                  \
+        return true;                                                                                \
+    }
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
+template <int N>
+RB_HOST_FMA bool fd_deriv_fma_n(const double *mdl, const double *q, const double *qd, const double *tau, double *qdd,
+                                double *dq, double *dqd, double *dtau) {
+    if constexpr (N <= kHostFdDerivMaxLinks) {
+        double a[N], b[N];
+        for (int j = 0; j < N; ++j) {
+            a[j] = q[j];
+            b[j] = qd[j];
+        }
+        dev::fd_deriv_eval<double, N, false>(
+            mdl, a, b,
+            [&](double(&tv)[N]) {
+                for (int j = 0; j < N; ++j) tv[j] = tau[j];
+            },
+            dq != nullptr, dqd != nullptr, dtau != nullptr,
+            [&](int j, double v) {
+                if (qdd) qdd[j] = v;
+            },
+            [&](int e, double v) { dq[e] = v; }, [&](int e, double v) { dqd[e] = v; },
+            [&](int e, double v) { dtau[e] = v; });
+        return true;
+    } else {
+        return false;
+    }
+}
+
+RB_HOST_FMA bool fd_deriv_fma(int n, const double *mdl, const double *q, const double *qd, const double *tau,
+                              double *qdd, double *dq, double *dqd, double *dtau) {
+    switch (n) {
+#define X(N) \
+    case N: return fd_deriv_fma_n<N>(mdl, q, qd, tau, qdd, dq, dqd, dtau);
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -124,6 +184,17 @@ bool host_fwd_kin(const Model &m, const double *pk, const double *q, double *pos
 
 bool host_jac(const Model &m, const double *pk, const double *q, double *J) {
     return host_eval_supported(m) && jac_fma(m.n, pk, q, J);
+}
+
+bool host_rnea_deriv(const Model &m, const double *pk, const double *q, const double *qd, const double *qdd,
+                     double *dtau_dq, double *dtau_dqd) {
+    return host_eval_supported(m) && rnea_deriv_fma(m.n, pk, q, qd, qdd, dtau_dq, dtau_dqd);
+}
+
+bool host_fd_deriv(const Model &m, const double *pk, const double *q, const double *qd, const double *tau, double *qdd,
+                   double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau) {
+    return host_eval_supported(m) && m.n <= kHostFdDerivMaxLinks &&
+           fd_deriv_fma(m.n, pk, q, qd, tau, qdd, dqdd_dq, dqdd_dqd, dqdd_dtau);
 }
 
 }  // namespace rbamd

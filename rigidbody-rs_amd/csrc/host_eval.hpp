@@ -19,4 +19,13 @@ bool host_crba(const Model &m, const double *pk, const double *q, double *H);
 bool host_fwd_kin(const Model &m, const double *pk, const double *q, double *pos);
 bool host_jac(const Model &m, const double *pk, const double *q, double *J);
 
+// Analytical derivatives (rnea_deriv_body.hip.hpp), n x n column-major, element i + n k =
+// d out_i / d in_k; a NULL output is not evaluated.  host_fd_deriv additionally needs the
+// mass-matrix forward dynamics (chains up to 12 links); it ignores the fd_form tuning.
+bool host_rnea_deriv(const Model &m, const double *pk, const double *q, const double *qd, const double *qdd,
+                     double *dtau_dq, double *dtau_dqd);
+bool host_fd_deriv(const Model &m, const double *pk, const double *q, const double *qd, const double *tau, double *qdd,
+                   double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau);
+constexpr int kHostFdDerivMaxLinks = 12;
+
 }  // namespace rbamd

@@ -141,6 +141,19 @@ int fd_form(const ModelShape &m, JitKind kind) {
 
 int jit_fd_form(const Model &m, JitKind kind) { return fd_form({m.n, m.serial_revolute()}, kind); }
 
+std::string jit_kind_unsupported(const Model &m, JitKind kind) {
+    if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv) return "";
+    const char *name = kind == JitKind::RneaDeriv ? "rnea_deriv" : "fd_deriv";
+    if (!m.serial_revolute())
+        return std::string(name) + ": no such kernel for this model: serial revolute chains only (kinematic trees, "
+               "prismatic joints and a floating base are not supported)";
+    if (kind == JitKind::FdDeriv && jit_fd_form(m, JitKind::Fd) != 2)
+        return std::string(name) + ": no such kernel for this model: it needs the mass-matrix forward dynamics "
+               "(serial chains up to 12 links, fd_form 2); this model has " + std::to_string(m.n) +
+               " links on the articulated-body form";
+    return "";
+}
+
 namespace {
 
 // The lane form a kernel of this model really takes for the requested pack (0 = the jit_pack policy).
@@ -234,7 +247,8 @@ int idfd_pack(bool f64, uint32_t B) {
 
 JitVariant jit_resolve(const Model &model, JitKind kind, bool f64, uint32_t B, bool tiled, bool fast_trig) {
     // only the forward-dynamics kinds' rules read `serial`: the others do not pay for the walk
-    const bool fd_kind = kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd;
+    const bool fd_kind = kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd;  // (the
+    // derivative kinds are one configuration per lane whatever the model: jit_pack, jit_model_pack)
     const ModelShape m{model.n, fd_kind && model.serial_revolute()};
     JitVariant v;
     v.kind = kind;
@@ -300,6 +314,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const JitKind kind = v.kind;
     const bool f64 = v.f64;
     const int pack = v.pack;
+    const bool deriv = kind == JitKind::RneaDeriv || kind == JitKind::FdDeriv;
+    if (deriv && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
         double *c = &pk[(size_t)i * kLinkStride];
@@ -309,7 +325,9 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const char *F = v.fast ? "true" : "false";
 
     // ---- what this variant's source is made of, decided before any text is written
-    const bool fdh = (kind == JitKind::Fd || kind == JitKind::RneaFd) && jit_fd_form(m) == 2;
+    // (FdDeriv exists on the mass-matrix form only and must define what the Fd kernel defines:
+    // its qdd is that kernel's, bit for bit)
+    const bool fdh = (kind == JitKind::Fd || kind == JitKind::RneaFd || kind == JitKind::FdDeriv) && jit_fd_form(m) == 2;
     // the rollout's forward dynamics follows the fd_form policy (mass-matrix form for short
     // serial chains) unless RB_VARIANT bit 8 (A/B) keeps the ABA
     const bool rollout_fdh = kind == JitKind::Rollout && jit_fd_form(m, kind) == 2 && !(tuning().jit_variant & 256);
@@ -338,7 +356,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     // memory-bound headline kernel gains nothing from fewer VALU, its sequential pair would need
     // 131 instead of 125 VGPRs (3 waves/SIMD instead of 4), and all its grid forms (pairs,
     // single tail, one per lane below 2^19) must stay bit-identical to each other.
-    const bool dyn = kind == JitKind::Rnea || kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd;
+    const bool dyn = kind == JitKind::Rnea || kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd ||
+                     deriv;
     // jit_variant bit 16384 (A/B): the centre-of-mass form for the fp64 RNEA too
     // rnea_lane_rev: the fp64 RNEA of serial chains longer than 8 links, whose per-link forces
     // hold one wave per SIMD (12 links 264 VGPRs, 30 links 496) and do not fit LDS either
@@ -416,7 +435,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         }
         o << "};\n";
     }
-    o << (kind == JitKind::Rnea                               ? "#include \"rnea_body.hip.hpp\"\n"
+    o << (deriv                                             ? "#include \"rnea_deriv_body.hip.hpp\"\n"
+          : kind == JitKind::Rnea                             ? "#include \"rnea_body.hip.hpp\"\n"
           : fdh                                               ? "#include \"fdh_body.hip.hpp\"\n"
           : (kind == JitKind::Fd || kind == JitKind::Rollout) ? "#include \"aba_body.hip.hpp\"\n"
           : kind == JitKind::Crba                             ? "#include \"crba_body.hip.hpp\"\n"
@@ -557,6 +577,21 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         } else {
             o << lane_prologue << "  rbamd::dev::aba_lane<T, N, " << F << ", Topo>" << lane_args;
         }
+    } else if (deriv) {
+        // one configuration per lane on SoA rows; a NULL output is neither evaluated nor stored
+        const bool fd = kind == JitKind::FdDeriv;
+        sig(fd ? "const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ tau, T *__restrict__ qdd, "
+                 "T *__restrict__ dq, T *__restrict__ dqd, T *__restrict__ dtau, uint32_t B, int64_t ld, int64_t bs"
+               : "const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ qdd, T *__restrict__ dq, "
+                 "T *__restrict__ dqd, uint32_t B, int64_t ld, int64_t bs");
+        o << lane_prologue;
+        if (fd)
+            o << "  rbamd::dev::fd_deriv_lane<T, N, " << F
+              << ">(kModel, q + o, qd + o, tau + o, qdd ? qdd + o : nullptr, dq ? dq + o : nullptr, "
+                 "dqd ? dqd + o : nullptr, dtau ? dtau + o : nullptr, threadIdx.x, ld);\n}\n";
+        else
+            o << "  rbamd::dev::rnea_deriv_lane<T, N, " << F
+              << ">(kModel, q + o, qd + o, qdd + o, dq ? dq + o : nullptr, dqd ? dqd + o : nullptr, threadIdx.x, ld);\n}\n";
     } else if (kind == JitKind::Rollout) {
         sig(rollout_params);
         if (pack == 4) {
@@ -646,6 +681,11 @@ bool rtc_compile(const std::string &src, const std::string &arch, bool no_licm, 
 
 bool jit_compile(const Model &m, const JitVariant &v, const std::string &arch, std::vector<char> *code,
                  std::string *error, std::string *final_src) {
+    const std::string why = jit_kind_unsupported(m, v.kind);
+    if (!why.empty()) {
+        *error = why;
+        return false;
+    }
     std::string src = jit_source(m, v, -1);
     const bool no_licm = jit_no_licm(m, v);
     if (!rtc_compile(src, arch, no_licm, code, error)) return false;

@@ -27,8 +27,17 @@ namespace rbamd {
 // (kinematic trees, prismatic joints -- Model::serial_revolute() false).
 // RneaFd: inverse + forward dynamics of the same (q, qd) in one launch (fdh_body.hip.hpp
 // fdh_idfd_eval), for models on the mass-matrix forward dynamics (jit_fd_form 2).
-enum class JitKind : int { Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6 };
-constexpr int kJitKinds = 7;
+// RneaDeriv / FdDeriv: analytical derivatives of the inverse / forward dynamics
+// (rnea_deriv_body.hip.hpp), serial revolute chains only -- FdDeriv on the mass-matrix forward
+// dynamics only (jit_kind_unsupported); they have no precompiled generic kernel.
+enum class JitKind : int {
+    Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8
+};
+constexpr int kJitKinds = 9;
+
+// Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds are
+// restricted here; jit_source returns an empty source for a model this refuses.
+std::string jit_kind_unsupported(const Model &m, JitKind kind);
 
 // One compiled kernel of a model: with the model and the tuning knobs (jit_key), everything its
 // source and compile flags depend on.  jit_resolve is the only producer.

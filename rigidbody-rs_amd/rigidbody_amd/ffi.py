@@ -97,7 +97,15 @@ _sig("multibody_jit_source", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, cty
 _sig("multibody_jit_compile", _i64, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p])
 _sig("multibody_jit_source_ex", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_char_p, _i64])
 _sig("multibody_jit_compile_ex", _i64, [_vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_char_p])
-KINDS = {"rnea": 0, "fd": 1, "crba": 2, "rollout": 3, "fwd_kin": 4, "jac": 5, "rnea_fd": 6}
+KINDS = {"rnea": 0, "fd": 1, "crba": 2, "rollout": 3, "fwd_kin": 4, "jac": 5, "rnea_fd": 6, "rnea_deriv": 7,
+         "fd_deriv": 8}
+for _t in ("f32", "f64"):
+    _sig(f"multibody_rnea_deriv_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
+    _sig(f"multibody_fd_deriv_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
+    _sig(f"multibody_rnea_deriv_batch_host_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64])
+    _sig(f"multibody_fd_deriv_batch_host_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64])
+_sig("multibody_rnea_deriv", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp])
+_sig("multibody_fd_deriv", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp])
 GENERAL_AXES, URDF_TREE, FLOATING_BASE = 1, 2, 4  # rigidbody_batch.h RB_MODEL_*
 _ip = ctypes.POINTER(ctypes.c_int)
 _sig("multibody_topology", ctypes.c_int, [_vp, _ip, _ip])
@@ -389,7 +397,67 @@ class Multibody:
     def jac(self, q) -> np.ndarray:
         return self.jac_raw(q).reshape(self.n, 6).T.copy()
 
+    def rnea_deriv(self, q, qd, qdd):
+        """multibody_rnea_deriv: (dtau_dq, dtau_dqd), each (n, n) with [i, k] = d tau_i / d q_k
+        (d qd_k), of tau = rnea(q, qd, qdd); one configuration, on the calling thread."""
+        q, qd, qdd = (_dvec(x, self.n) for x in (q, qd, qdd))
+        outs = [np.empty(self.n * self.n) for _ in range(2)]
+        _check(_lib.multibody_rnea_deriv(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, qdd, *outs)]), "rnea_deriv")
+        return tuple(o.reshape(self.n, self.n).T.copy() for o in outs)
+
+    def fd_deriv(self, q, qd, tau):
+        """multibody_fd_deriv: (qdd, dqdd_dq, dqdd_dqd, dqdd_dtau) of qdd = fd(q, qd, tau); the
+        matrices (n, n) with [i, k] = d qdd_i / d q_k (d qd_k, d tau_k); one configuration, host."""
+        q, qd, tau = (_dvec(x, self.n) for x in (q, qd, tau))
+        qdd = np.empty(self.n)
+        outs = [np.empty(self.n * self.n) for _ in range(3)]
+        _check(_lib.multibody_fd_deriv(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau, qdd, *outs)]), "fd_deriv")
+        return (qdd, *(o.reshape(self.n, self.n).T.copy() for o in outs))
+
     # ------------------------------------------------------- batched, device [n, B]
+    def _mat_out(self, q):
+        """An [n*n, B] matrix output with q's leading dimension."""
+        return torch.empty((self.n * self.n, _ld(q)), dtype=q.dtype, device=q.device)[:, :q.shape[1]]
+
+    def rnea_deriv_batch(self, q, qd, qdd, want=("q", "qd"), stream=None):
+        """multibody_rnea_deriv_batch_*: the derivatives of tau = rnea(q, qd, qdd) named in `want`
+        ("q": d tau / d q, "qd": d tau / d qd), in that order, as [n*n, B] tensors -- row i + n k of
+        column b is d tau_i / d q_k of configuration b.  One launch; a matrix not wanted is not
+        computed."""
+        want = tuple(want)
+        if not want or any(w not in ("q", "qd") for w in want) or len(set(want)) != len(want):
+            raise ValueError('want must name "q" and / or "qd"')
+        q = _soa(q, self.n, "q")
+        B = q.shape[1]
+        qd = _soa(qd, self.n, "qd", q.dtype, B)
+        qdd = _soa(qdd, self.n, "qdd", q.dtype, B)
+        ld = _same_ld((q, qd, qdd))
+        dev = _one_device((q, qd, qdd))
+        outs = {w: self._mat_out(q) for w in want}
+        ptr = {w: (outs[w].data_ptr() if w in outs else None) for w in ("q", "qd")}
+        fn = getattr(_lib, f"multibody_rnea_deriv_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), ptr["q"], ptr["qd"], B, ld,
+                      _stream_ptr(stream, dev)), "rnea_deriv_batch")
+        return tuple(outs[w] for w in want)
+
+    def fd_deriv_batch(self, q, qd, tau, stream=None):
+        """multibody_fd_deriv_batch_*: (qdd [n, B], dqdd_dq, dqdd_dqd, dqdd_dtau [n*n, B]) of
+        qdd = fd(q, qd, tau) in one launch; qdd is fd_batch's, bit for bit."""
+        q = _soa(q, self.n, "q")
+        B = q.shape[1]
+        qd = _soa(qd, self.n, "qd", q.dtype, B)
+        tau = _soa(tau, self.n, "tau", q.dtype, B)
+        ld = _same_ld((q, qd, tau))
+        dev = _one_device((q, qd, tau))
+        qdd = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
+        mats = [self._mat_out(q) for _ in range(3)]
+        fn = getattr(_lib, f"multibody_fd_deriv_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), qdd.data_ptr(),
+                      *[m.data_ptr() for m in mats], B, ld, _stream_ptr(stream, dev)), "fd_deriv_batch")
+        return (qdd, *mats)
+
     def rnea_batch(self, q, qd, qdd, out=None, stream=None):
         q = _soa(q, self.n, "q")
         B = q.shape[1]
@@ -592,6 +660,24 @@ class Multibody:
         ptr = _fp if f32 else _dp
         _check(fn(self._h, *[a.ctypes.data_as(ptr) for a in arrs + outs], B), "rnea_fd_batch_host")
         return outs[0], outs[1]
+
+    def rnea_deriv_batch_host(self, q, qd, qdd, dtype=np.float64):
+        """Blocking host form of rnea_deriv_batch: (dtau_dq, dtau_dqd) as [n*n, B] numpy arrays."""
+        arrs = _host_soa((q, qd, qdd), self.n, dtype)
+        B = arrs[0].shape[1]
+        outs = [np.empty((self.n * self.n, B), dtype=arrs[0].dtype) for _ in range(2)]
+        fn = getattr(_lib, f"multibody_rnea_deriv_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in arrs + outs], B), "rnea_deriv_batch_host")
+        return outs[0], outs[1]
+
+    def fd_deriv_batch_host(self, q, qd, tau, dtype=np.float64):
+        """Blocking host form of fd_deriv_batch: (qdd [n, B], dqdd_dq, dqdd_dqd, dqdd_dtau [n*n, B])."""
+        arrs = _host_soa((q, qd, tau), self.n, dtype)
+        B = arrs[0].shape[1]
+        outs = [np.empty_like(arrs[0])] + [np.empty((self.n * self.n, B), dtype=arrs[0].dtype) for _ in range(3)]
+        fn = getattr(_lib, f"multibody_fd_deriv_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in arrs + outs], B), "fd_deriv_batch_host")
+        return tuple(outs)
 
     def _host_call(self, kind, ins, dtype):
         arrs = _host_soa(ins, self.n, dtype)
