@@ -9,16 +9,13 @@
 // caller asks for the GPU (tuning single_gpu).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <fstream>
 #include <initializer_list>
 #include <map>
-#include <mutex>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -29,6 +26,7 @@
 #include "model.hpp"
 #include "tuning.hpp"
 #include "jit.hpp"
+#include "device_cache.hpp"
 #include "host_eval.hpp"
 
 #include "fr3_embedded.inc"  // kFr3Urdf: compact FR3 description (tools/gen_fixtures.py)
@@ -70,37 +68,13 @@ bool fast_trig() {
     return fast;
 }
 
-struct DeviceConsts {
-    float *f32 = nullptr;
-    double *f64 = nullptr;
-};
-
 }  // namespace
 
 struct Multibody {
     rbamd::Model model;
     std::vector<float> pk32;
     std::vector<double> pk64;
-    mutable std::mutex mu;
-    mutable std::map<int, DeviceConsts> dev;
-    // model-specialised hipRTC kernels, keyed by (device, kind, dtype, trig, tuning tag, form)
-    mutable std::map<std::string, rbamd::JitKernel> jit;
-    mutable std::map<std::string, int> jit_device;
-    // per-launch fast path of jit_get: [device][kind][f64][fast trig][pack][tail, nt] of the variant ->
-    // the kernel resolved under one tuning generation, published as ONE pointer to a record
-    // {generation, kernel}.  There is one record per (slot, kernel) pair, so the records are
-    // bounded by slots x kernels however often the tuning changes: a record's kernel never
-    // changes, its generation is re-stamped only when ITS slot resolves to that kernel again,
-    // and records live in jit_pub (std::map nodes never move) until free.  A reader that sees
-    // the current generation in the record its slot points at has that slot's kernel.
-    struct JitPub {
-        std::atomic<unsigned> gen{0};
-        const rbamd::JitKernel *jk = nullptr;
-    };
-    mutable std::map<std::pair<const void *, const rbamd::JitKernel *>, JitPub> jit_pub;
-    mutable std::atomic<const JitPub *> jit_fast[16][rbamd::kJitKinds][2][2][6][4] = {};  // last: tail > 0, nt override
-    // device_consts fast path: the uploaded constant blocks per device (set once, never moved)
-    mutable std::atomic<const void *> dc_fast[16][2] = {};
+    mutable rbamd::DeviceCache cache;  // constants and hipRTC kernels on the devices it has run on
 };
 
 namespace {
@@ -132,85 +106,11 @@ Multibody *make(rbamd::Model &&m) {
 // Device copy of the packed model constants on the current device (uploaded once).
 template <typename T>
 int device_consts(const Multibody *mb, const T **out) {
-    int d = 0;
-    hipError_t e = hipGetDevice(&d);
-    if (e != hipSuccess) return hip_err(e, "hipGetDevice");
-    std::atomic<const void *> *fastp = (d >= 0 && d < 16) ? &mb->dc_fast[d][sizeof(T) == 8 ? 1 : 0] : nullptr;
-    if (fastp) {
-        if (const void *p = fastp->load(std::memory_order_acquire)) {
-            *out = static_cast<const T *>(p);
-            return RB_OK;
-        }
-    }
-    std::lock_guard<std::mutex> lk(mb->mu);
-    DeviceConsts &dc = mb->dev[d];
-    T **block;
-    const std::vector<T> *host;
-    if constexpr (sizeof(T) == 4) {
-        block = &dc.f32;
-        host = &mb->pk32;
-    } else {
-        block = &dc.f64;
-        host = &mb->pk64;
-    }
-    if (!*block) {
-        void *p = nullptr;
-        size_t bytes = host->size() * sizeof(T);
-        if ((e = hipMalloc(&p, bytes)) != hipSuccess) return hip_err(e, "hipMalloc(model)");
-        if ((e = hipMemcpy(p, host->data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-            (void)hipFree(p);
-            return hip_err(e, "hipMemcpy(model)");
-        }
-        *block = static_cast<T *>(p);
-    }
-    *out = *block;
-    if (fastp) fastp->store(*block, std::memory_order_release);
-    return RB_OK;
-}
-
-// The hipRTC kernel of variant `v` (jit.hpp jit_resolve) for this model on the current device,
-// or nullptr (the precompiled generic kernel then runs).
-const rbamd::JitKernel *jit_get(const Multibody *mb, const rbamd::JitVariant &v) {
-    if (!rbamd::jit_enabled()) return nullptr;
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess) return nullptr;
-    std::atomic<const Multibody::JitPub *> *slot = nullptr;
-    if (d >= 0 && d < 16 && (int)v.kind >= 0 && (int)v.kind < rbamd::kJitKinds && v.pack >= 0 && v.pack < 6) {
-        slot = &mb->jit_fast[d][(int)v.kind][v.f64 ? 1 : 0][v.fast ? 1 : 0][v.pack][(v.tail > 0 ? 1 : 0) | (v.nt >= 0 ? 2 : 0)];
-        if (const Multibody::JitPub *p = slot->load(std::memory_order_acquire))
-            if (p->gen.load(std::memory_order_acquire) == rbamd::tuning_generation()) return p->jk;
-    }
-    std::lock_guard<std::mutex> lk(mb->mu);
-    // The tuning generation is a sequence count (tuning.cpp): odd while rb_set_tuning writes,
-    // bumped again after.  The key and the kernel source both read the tuning knobs, so they are
-    // resolved between two reads of one even generation; a write in between resolves again (a
-    // kernel built from a mix of two tunings is never stored under either key).
-    for (;;) {
-        const unsigned gen = rbamd::tuning_generation_stable();
-        const std::string key = std::to_string(d) + rbamd::jit_key(mb->model, v);
-        auto it = mb->jit.find(key);
-        if (it == mb->jit.end()) {
-            rbamd::JitKernel built = rbamd::jit_build(mb->model, v);
-            if (rbamd::tuning_generation() != gen) {  // the tuning moved under the build
-                if (built.module) (void)hipModuleUnload(built.module);
-                continue;
-            }
-            it = mb->jit.emplace(key, std::move(built)).first;
-            mb->jit_device[key] = d;
-        }
-        const rbamd::JitKernel *res = it->second.function ? &it->second : nullptr;
-        if (rbamd::tuning_generation() != gen) continue;
-        if (slot && res) {
-            // jk is written once, when the record is created (the key holds the same pointer), and
-            // never again: fast-path readers may hold the record while this re-stamps gen
-            auto ins = mb->jit_pub.try_emplace({(const void *)slot, res});
-            Multibody::JitPub &rec = ins.first->second;
-            if (ins.second) rec.jk = res;
-            rec.gen.store(gen, std::memory_order_release);
-            slot->store(&rec, std::memory_order_release);
-        }
-        return res;
-    }
+    const char *where = nullptr;
+    hipError_t e;
+    if constexpr (sizeof(T) == 4) e = mb->cache.consts(mb->pk32, out, &where);
+    else e = mb->cache.consts(mb->pk64, out, &where);
+    return e == hipSuccess ? RB_OK : hip_err(e, where);
 }
 
 // A tree / prismatic model has no precompiled kernel: without its hipRTC kernel the launch
@@ -220,9 +120,7 @@ hipError_t no_generic(const Multibody *mb, const char *what = "kinematic-tree / 
     if (!rbamd::jit_enabled()) {
         why += ", which are disabled (RB_JIT=0 / rb_set_tuning(\"jit\", 0))";
     } else {
-        std::lock_guard<std::mutex> lk(mb->mu);
-        for (auto &kv : mb->jit)
-            if (!kv.second.error.empty()) why += "; hipRTC: " + kv.second.error.substr(0, 400);
+        for (const std::string &err : mb->cache.jit_errors()) why += "; hipRTC: " + err.substr(0, 400);
     }
     t_launch_note = why;
     return hipErrorNotSupported;
@@ -248,7 +146,7 @@ const rbamd::JitKernel *kernel_for(const Multibody *mb, rbamd::JitKind kind, boo
     // the fused inverse + forward dynamics exists for serial chains on the mass-matrix form only
     // (jit_fd_form is 1 for this kind on every model that is not a serial revolute chain)
     if (kind == rbamd::JitKind::RneaFd && rbamd::jit_fd_form(mb->model, rbamd::JitKind::RneaFd) != 2) return nullptr;
-    return jit_get(mb, rbamd::jit_resolve(mb->model, kind, f64, B, tiled, fast_trig()));
+    return mb->cache.kernel(mb->model, rbamd::jit_resolve(mb->model, kind, f64, B, tiled, fast_trig()));
 }
 
 hipError_t jit_launch(const rbamd::JitKernel *jk, uint32_t B, void **args, hipStream_t s) {
@@ -266,33 +164,42 @@ TileStrides tile_strides(bool tiled, int64_t ld, int64_t rows_in, int64_t rows_o
     return {256, rows_in * 256, rows_out * 256};
 }
 
+// One launch of B configurations of `kind`: the model-specialised kernel with `args` (pointers
+// to the caller's locals, in the kernel's parameter order) where kernel_for has one, else
+// `fallback()` -- the precompiled launcher, no_generic, or another launcher.
+template <size_t N, typename Fallback>
+hipError_t launch_any(const Multibody *mb, rbamd::JitKind kind, bool f64, uint32_t B, bool tiled, hipStream_t s,
+                      void *(&args)[N], Fallback fallback) {
+    if (B == 0) return hipSuccess;
+    if (const rbamd::JitKernel *jk = kernel_for(mb, kind, f64, B, tiled)) return jit_launch(jk, B, args, s);
+    return fallback();
+}
+
 // tiled: the [ceil(B/256)][n][256] layout (kernels.hpp); the JIT lane kernels and the
 // generic lane kernels take it through their block stride (the generic grid-stride RNEA is
 // SoA-only and never chosen for it).
 template <typename T>
 hipError_t launch_rnea_any(const Multibody *mb, const T *mdl, const T *q, const T *qd, const T *qdd, T *tau,
                            uint32_t B, int64_t ld, hipStream_t s, bool tiled = false) {
-    if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Rnea, sizeof(T) == 8, B, tiled)) {
-        TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
-        void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&tau, (void *)&B, (void *)&st.lda, (void *)&st.bs_in};
-        return jit_launch(jk, B, args, s);
-    }
-    if (!mb->model.serial_revolute()) return no_generic(mb);
-    return rbamd::launch_rnea<T>(mb->model.n, mdl, q, qd, qdd, tau, B, ld, s, fast_trig(), tiled);
+    const int n = mb->model.n;
+    TileStrides st = tile_strides(tiled, ld, n, n);
+    void *args[] = {&q, &qd, &qdd, &tau, &B, &st.lda, &st.bs_in};
+    return launch_any(mb, rbamd::JitKind::Rnea, sizeof(T) == 8, B, tiled, s, args, [&] {
+        if (!mb->model.serial_revolute()) return no_generic(mb);
+        return rbamd::launch_rnea<T>(n, mdl, q, qd, qdd, tau, B, ld, s, fast_trig(), tiled);
+    });
 }
 
 template <typename T>
 hipError_t launch_fd_any(const Multibody *mb, const T *mdl, const T *q, const T *qd, const T *tau, T *qdd,
                          uint32_t B, int64_t ld, hipStream_t s, bool tiled = false) {
-    if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Fd, sizeof(T) == 8, B, tiled)) {
-        TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
-        void *args[] = {(void *)&q, (void *)&qd, (void *)&tau, (void *)&qdd, (void *)&B, (void *)&st.lda, (void *)&st.bs_in};
-        return jit_launch(jk, B, args, s);
-    }
-    if (!mb->model.serial_revolute()) return no_generic(mb);
-    return rbamd::launch_aba<T>(mb->model.n, mdl, q, qd, tau, qdd, B, ld, s, fast_trig(), tiled);
+    const int n = mb->model.n;
+    TileStrides st = tile_strides(tiled, ld, n, n);
+    void *args[] = {&q, &qd, &tau, &qdd, &B, &st.lda, &st.bs_in};
+    return launch_any(mb, rbamd::JitKind::Fd, sizeof(T) == 8, B, tiled, s, args, [&] {
+        if (!mb->model.serial_revolute()) return no_generic(mb);
+        return rbamd::launch_aba<T>(n, mdl, q, qd, tau, qdd, B, ld, s, fast_trig(), tiled);
+    });
 }
 
 // Inverse + forward dynamics of the same (q, qd) (config 4's pair): one fused hipRTC launch
@@ -302,60 +209,49 @@ hipError_t launch_fd_any(const Multibody *mb, const T *mdl, const T *q, const T 
 template <typename T>
 hipError_t launch_idfd_any(const Multibody *mb, const T *mdl, const T *q, const T *qd, const T *qdd, const T *tau_in,
                            T *tau, T *qdd_out, uint32_t B, int64_t ld, hipStream_t s, bool tiled = false) {
-    if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::RneaFd, sizeof(T) == 8, B, tiled)) {
-        TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
-        void *args[] = {(void *)&q,   (void *)&qd, (void *)&qdd,  (void *)&tau_in, (void *)&tau,
-                        (void *)&qdd_out, (void *)&B, (void *)&st.lda, (void *)&st.bs_in};
-        return jit_launch(jk, B, args, s);
-    }
-    hipError_t e = launch_rnea_any<T>(mb, mdl, q, qd, qdd, tau, B, ld, s, tiled);
-    if (e != hipSuccess) return e;
-    return launch_fd_any<T>(mb, mdl, q, qd, tau_in, qdd_out, B, ld, s, tiled);
+    TileStrides st = tile_strides(tiled, ld, mb->model.n, mb->model.n);
+    void *args[] = {&q, &qd, &qdd, &tau_in, &tau, &qdd_out, &B, &st.lda, &st.bs_in};
+    return launch_any(mb, rbamd::JitKind::RneaFd, sizeof(T) == 8, B, tiled, s, args, [&] {
+        hipError_t e = launch_rnea_any<T>(mb, mdl, q, qd, qdd, tau, B, ld, s, tiled);
+        if (e != hipSuccess) return e;
+        return launch_fd_any<T>(mb, mdl, q, qd, tau_in, qdd_out, B, ld, s, tiled);
+    });
 }
 
 template <typename T>
 hipError_t launch_rollout_any(const Multibody *mb, const T *mdl, T *q, T *qd, const T *tau_seq, T dt, int K, T *traj,
                               uint32_t B, int64_t ld, hipStream_t s) {
-    if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Rollout, sizeof(T) == 8, B, false)) {
-        void *args[] = {(void *)&q, (void *)&qd, (void *)&tau_seq, (void *)&dt, (void *)&K, (void *)&traj,
-                        (void *)&B, (void *)&ld};
-        return jit_launch(jk, B, args, s);
-    }
-    if (!mb->model.serial_revolute()) return no_generic(mb);
-    return rbamd::launch_rollout<T>(mb->model.n, mdl, q, qd, tau_seq, dt, K, traj, B, ld, s, fast_trig());
+    void *args[] = {&q, &qd, &tau_seq, &dt, &K, &traj, &B, &ld};
+    return launch_any(mb, rbamd::JitKind::Rollout, sizeof(T) == 8, B, false, s, args, [&] {
+        if (!mb->model.serial_revolute()) return no_generic(mb);
+        return rbamd::launch_rollout<T>(mb->model.n, mdl, q, qd, tau_seq, dt, K, traj, B, ld, s, fast_trig());
+    });
 }
 
 template <typename T>
 hipError_t launch_crba_any(const Multibody *mb, const T *mdl, const T *q, T *H, uint32_t B, int64_t ld,
                            hipStream_t s, bool tiled = false) {
-    if (B == 0) return hipSuccess;
-    if (const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::Crba, sizeof(T) == 8, B, tiled)) {
-        const int64_t n = mb->model.n;
-        TileStrides st = tile_strides(tiled, ld, n, n * n);
-        void *args[] = {(void *)&q, (void *)&H, (void *)&B, (void *)&st.lda, (void *)&st.bs_in, (void *)&st.bs_out};
-        return jit_launch(jk, B, args, s);
-    }
-    if (!mb->model.serial_revolute()) return no_generic(mb);
-    return rbamd::launch_crba<T>(mb->model.n, mdl, q, H, B, ld, s, tiled);
+    const int64_t n = mb->model.n;
+    TileStrides st = tile_strides(tiled, ld, n, n * n);
+    void *args[] = {&q, &H, &B, &st.lda, &st.bs_in, &st.bs_out};
+    return launch_any(mb, rbamd::JitKind::Crba, sizeof(T) == 8, B, tiled, s, args, [&] {
+        if (!mb->model.serial_revolute()) return no_generic(mb);
+        return rbamd::launch_crba<T>(mb->model.n, mdl, q, H, B, ld, s, tiled);
+    });
 }
 
 template <typename T>
 hipError_t launch_kin_any(const Multibody *mb, bool jac, const T *mdl, const T *q, T *out, uint32_t B, int64_t ld,
                           hipStream_t s, bool tiled = false) {
-    if (B == 0) return hipSuccess;
-    const bool fast = sizeof(T) == 4 && fast_trig();
-    const rbamd::JitKernel *jk =
-        kernel_for(mb, jac ? rbamd::JitKind::Jac : rbamd::JitKind::FwdKin, sizeof(T) == 8, B, tiled);
-    if (!jk && mb->model.serial_revolute())
-        return jac ? rbamd::launch_jac<T>(mb->model.n, mdl, q, out, B, ld, s, fast, tiled)
-                   : rbamd::launch_fwd_kin<T>(mb->model.n, mdl, q, out, B, ld, s, fast, tiled);
-    if (!jk) return no_generic(mb);
     const int64_t n = mb->model.n;
     TileStrides st = tile_strides(tiled, ld, n, jac ? 6 * n : 3);
-    void *args[] = {(void *)&q, (void *)&out, (void *)&B, (void *)&st.lda, (void *)&st.bs_in, (void *)&st.bs_out};
-    return jit_launch(jk, B, args, s);
+    void *args[] = {&q, &out, &B, &st.lda, &st.bs_in, &st.bs_out};
+    return launch_any(mb, jac ? rbamd::JitKind::Jac : rbamd::JitKind::FwdKin, sizeof(T) == 8, B, tiled, s, args, [&] {
+        if (!mb->model.serial_revolute()) return no_generic(mb);
+        const bool fast = sizeof(T) == 4 && fast_trig();
+        return jac ? rbamd::launch_jac<T>(mb->model.n, mdl, q, out, B, ld, s, fast, tiled)
+                   : rbamd::launch_fwd_kin<T>(mb->model.n, mdl, q, out, B, ld, s, fast, tiled);
+    });
 }
 
 // Analytical derivatives (rnea_deriv_body.hip.hpp): model-specialised kernels only, SoA rows; a
@@ -364,24 +260,19 @@ hipError_t launch_kin_any(const Multibody *mb, bool jac, const T *mdl, const T *
 template <typename T>
 hipError_t launch_rnea_deriv(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *dq, T *dqd, uint32_t B,
                              int64_t ld, hipStream_t s) {
-    if (B == 0) return hipSuccess;
-    const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::RneaDeriv, sizeof(T) == 8, B, false);
-    if (!jk) return no_generic(mb, "the dynamics derivatives run");
     int64_t bs = 256;
-    void *args[] = {(void *)&q, (void *)&qd, (void *)&qdd, (void *)&dq, (void *)&dqd, (void *)&B, (void *)&ld, (void *)&bs};
-    return jit_launch(jk, B, args, s);
+    void *args[] = {&q, &qd, &qdd, &dq, &dqd, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::RneaDeriv, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the dynamics derivatives run"); });
 }
 
 template <typename T>
 hipError_t launch_fd_deriv(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, T *dq, T *dqd, T *dtau,
                            uint32_t B, int64_t ld, hipStream_t s) {
-    if (B == 0) return hipSuccess;
-    const rbamd::JitKernel *jk = kernel_for(mb, rbamd::JitKind::FdDeriv, sizeof(T) == 8, B, false);
-    if (!jk) return no_generic(mb, "the dynamics derivatives run");
     int64_t bs = 256;
-    void *args[] = {(void *)&q,   (void *)&qd,   (void *)&tau, (void *)&qdd, (void *)&dq,
-                    (void *)&dqd, (void *)&dtau, (void *)&B,   (void *)&ld,  (void *)&bs};
-    return jit_launch(jk, B, args, s);
+    void *args[] = {&q, &qd, &tau, &qdd, &dq, &dqd, &dtau, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::FdDeriv, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the dynamics derivatives run"); });
 }
 
 constexpr int64_t kChunk = int64_t(1) << 28;  // per-launch batch cap: b * sizeof(T) < 2^32
@@ -510,10 +401,22 @@ int no_null(std::initializer_list<const void *> arrays) {
     return RB_OK;
 }
 
+// Where configuration b0 (a multiple of 256) starts in the arrays of one call: at(p, rows) for an
+// array of `rows` rows per configuration -- b0 elements along SoA rows, b0 * rows into the tiled
+// layout; a NULL (optional) array stays NULL.
+struct ChunkAt {
+    int64_t b0;
+    bool tiled;
+    template <typename P>
+    P *operator()(P *p, int64_t rows) const {
+        return p ? p + b0 * (tiled ? rows : 1) : nullptr;
+    }
+};
+
 // The spine of every batched entry point.  Argument errors are reported in this order: handle,
 // batch, ld (check_batch), then the entry point's own arrays (`args_ok`: its NULL check, and
-// whatever else it refuses), then the device.  `launch(mdl, b0, nb)` enqueues configurations
-// [b0, b0 + nb) -- at most kChunk of them, b0 a multiple of 256; `where` labels its failure.
+// whatever else it refuses), then the device.  `launch(mdl, at, nb)` enqueues the nb (at most
+// kChunk) configurations that start where `at` points; `where` labels its failure.
 template <typename T, typename Check, typename Launch>
 int batch_call(const Multibody *mb, int64_t batch, int64_t ld, bool tiled, Check args_ok, const char *where,
                Launch launch) {
@@ -524,7 +427,7 @@ int batch_call(const Multibody *mb, int64_t batch, int64_t ld, bool tiled, Check
     const T *mdl = nullptr;
     if ((rc = device_consts<T>(mb, &mdl))) return rc;
     return chunked<T>(batch, [&](int64_t b0, uint32_t nb) {
-        hipError_t e = launch(mdl, b0, nb);
+        hipError_t e = launch(mdl, ChunkAt{b0, tiled}, nb);
         return e == hipSuccess ? RB_OK : hip_err(e, where);
     });
 }
@@ -533,9 +436,10 @@ template <typename T>
 int rnea_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *tau, int64_t batch,
                int64_t ld, void *stream, bool tiled = false) {
     return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, qd, qdd, tau}); }, "rnea launch",
-                         [&](const T *mdl, int64_t b0, uint32_t nb) {
-        const int64_t o = b0 * (tiled ? mb->model.n : 1);  // element offset of configuration b0 (b0 % 256 == 0)
-        return launch_rnea_any<T>(mb, mdl, q + o, qd + o, qdd + o, tau + o, nb, ld, (hipStream_t)stream, tiled);
+                         [&](const T *mdl, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_rnea_any<T>(mb, mdl, at(q, n), at(qd, n), at(qdd, n), at(tau, n), nb, ld, (hipStream_t)stream,
+                                  tiled);
     });
 }
 
@@ -543,9 +447,10 @@ template <typename T>
 int fd_batch(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, int64_t batch,
              int64_t ld, void *stream, bool tiled = false) {
     return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, qd, tau, qdd}); }, "aba launch",
-                         [&](const T *mdl, int64_t b0, uint32_t nb) {
-        const int64_t o = b0 * (tiled ? mb->model.n : 1);
-        return launch_fd_any<T>(mb, mdl, q + o, qd + o, tau + o, qdd + o, nb, ld, (hipStream_t)stream, tiled);
+                         [&](const T *mdl, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_fd_any<T>(mb, mdl, at(q, n), at(qd, n), at(tau, n), at(qdd, n), nb, ld, (hipStream_t)stream,
+                                tiled);
     });
 }
 
@@ -562,10 +467,10 @@ int idfd_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, const
         if (tau == qdd_out) return set_err(RB_ERR_ARG, "rnea_fd: tau and qdd_out are the same array");
         return (int)RB_OK;
     };
-    return batch_call<T>(mb, batch, ld, tiled, args_ok, "rnea_fd launch", [&](const T *mdl, int64_t b0, uint32_t nb) {
-        const int64_t o = b0 * (tiled ? mb->model.n : 1);
-        return launch_idfd_any<T>(mb, mdl, q + o, qd + o, qdd + o, tau_in + o, tau + o, qdd_out + o, nb, ld,
-                                  (hipStream_t)stream, tiled);
+    return batch_call<T>(mb, batch, ld, tiled, args_ok, "rnea_fd launch", [&](const T *mdl, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_idfd_any<T>(mb, mdl, at(q, n), at(qd, n), at(qdd, n), at(tau_in, n), at(tau, n), at(qdd_out, n),
+                                  nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
@@ -601,9 +506,10 @@ int rnea_deriv_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd,
     auto args_ok = [&] {
         return deriv_args_ok<T>(mb, rbamd::JitKind::RneaDeriv, "rnea_deriv", {q, qd, qdd}, {dq, dqd});
     };
-    return batch_call<T>(mb, batch, ld, false, args_ok, "rnea_deriv launch", [&](const T *, int64_t b0, uint32_t nb) {
-        return launch_rnea_deriv<T>(mb, q + b0, qd + b0, qdd + b0, dq ? dq + b0 : nullptr, dqd ? dqd + b0 : nullptr, nb,
-                                    ld, (hipStream_t)stream);
+    return batch_call<T>(mb, batch, ld, false, args_ok, "rnea_deriv launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n, nn = n * n;
+        return launch_rnea_deriv<T>(mb, at(q, n), at(qd, n), at(qdd, n), at(dq, nn), at(dqd, nn), nb, ld,
+                                    (hipStream_t)stream);
     });
 }
 
@@ -613,9 +519,10 @@ int fd_deriv_batch(const Multibody *mb, const T *q, const T *qd, const T *tau, T
     auto args_ok = [&] {
         return deriv_args_ok<T>(mb, rbamd::JitKind::FdDeriv, "fd_deriv", {q, qd, tau}, {qdd, dq, dqd, dtau});
     };
-    return batch_call<T>(mb, batch, ld, false, args_ok, "fd_deriv launch", [&](const T *, int64_t b0, uint32_t nb) {
-        return launch_fd_deriv<T>(mb, q + b0, qd + b0, tau + b0, qdd ? qdd + b0 : nullptr, dq ? dq + b0 : nullptr,
-                                  dqd ? dqd + b0 : nullptr, dtau ? dtau + b0 : nullptr, nb, ld, (hipStream_t)stream);
+    return batch_call<T>(mb, batch, ld, false, args_ok, "fd_deriv launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n, nn = n * n;
+        return launch_fd_deriv<T>(mb, at(q, n), at(qd, n), at(tau, n), at(qdd, n), at(dq, nn), at(dqd, nn),
+                                  at(dtau, nn), nb, ld, (hipStream_t)stream);
     });
 }
 
@@ -629,19 +536,19 @@ int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt,
     if (K < 0) return set_err(RB_ERR_ARG, "negative step count");
     if (K == 0) return RB_OK;
     return batch_call<T>(mb, batch, ld, false, [&] { return no_null({q, qd, tau_seq}); }, "rollout launch",
-                         [&](const T *mdl, int64_t b0, uint32_t nb) {
-        return launch_rollout_any<T>(mb, mdl, q + b0, qd + b0, tau_seq + b0, (T)dt, K, traj ? traj + b0 : nullptr, nb,
-                                     ld, (hipStream_t)stream);
+                         [&](const T *mdl, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;  // tau_seq and traj: K * n rows, SoA only
+        return launch_rollout_any<T>(mb, mdl, at(q, n), at(qd, n), at(tau_seq, K * n), (T)dt, K, at(traj, K * n), nb, ld,
+                                     (hipStream_t)stream);
     });
 }
 
 template <typename T>
 int crba_batch(const Multibody *mb, const T *q, T *H, int64_t batch, int64_t ld, void *stream, bool tiled = false) {
     return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, H}); }, "crba launch",
-                         [&](const T *mdl, int64_t b0, uint32_t nb) {
-        // element offsets of configuration b0 (b0 % 256 == 0) in the input / output arrays
-        const int64_t n = mb->model.n, pin = tiled ? n : 1, pout = tiled ? n * n : 1;
-        return launch_crba_any<T>(mb, mdl, q + b0 * pin, H + b0 * pout, nb, ld, (hipStream_t)stream, tiled);
+                         [&](const T *mdl, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_crba_any<T>(mb, mdl, at(q, n), at(H, n * n), nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
@@ -649,9 +556,9 @@ template <typename T>
 int kin_batch(const Multibody *mb, bool jac, const T *q, T *out, int64_t batch, int64_t ld, void *stream,
               bool tiled = false) {
     return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, out}); }, jac ? "jac launch" : "fwd_kin launch",
-                         [&](const T *mdl, int64_t b0, uint32_t nb) {
-        const int64_t n = mb->model.n, pin = tiled ? n : 1, pout = tiled ? (jac ? 6 * n : 3) : 1;
-        return launch_kin_any<T>(mb, jac, mdl, q + b0 * pin, out + b0 * pout, nb, ld, (hipStream_t)stream, tiled);
+                         [&](const T *mdl, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_kin_any<T>(mb, jac, mdl, at(q, n), at(out, jac ? 6 * n : 3), nb, ld, (hipStream_t)stream, tiled);
     });
 }
 
@@ -667,84 +574,25 @@ Multibody *new_from_text(const std::string &xml, unsigned flags = 0) {
 }  // namespace
 
 namespace {
-// nin input and nout output [n][batch] host arrays; launch(d_in, d_out, stream) gets the device
-// copies of the inputs (consecutive) and room for the outputs (consecutive).
-template <typename T, typename Launch>
-int host_batch(const Multibody *mb, const T *const *in, int nin, T *const *out, int nout, int64_t batch,
-               Launch launch) {
+// The blocking host-pointer forms: SoA rows x[j * batch + b] in host memory, copied to a scratch
+// device buffer on a private stream, evaluated by the batched kernels, copied back.  NIN inputs
+// of n rows; NOUT outputs of rows[k] rows, a NULL one skipped where null_outputs allows it (it
+// takes no scratch: the device offsets depend on which outputs are present).  check() is the
+// entry point's own argument check, after the handle / batch / NULL checks and before any device
+// work; launch(d_in[], d_out[], stream) gets the device arrays (NULL for a skipped output).
+template <typename T, int NIN, int NOUT, typename Check, typename Launch>
+int host_call(const Multibody *mb, const T *const (&in)[NIN], T *const (&out)[NOUT], const int64_t (&rows)[NOUT],
+              bool null_outputs, int64_t batch, Check check, Launch launch) {
     int rc = check_batch(mb, batch, batch);
     if (rc) return rc;
     if (batch == 0) return RB_OK;
-    for (int k = 0; k < nin; ++k)
-        if (!in[k]) return set_err(RB_ERR_NULL, "NULL array");
-    for (int k = 0; k < nout; ++k)
-        if (!out[k]) return set_err(RB_ERR_NULL, "NULL array");
-    const size_t per = (size_t)mb->model.n * (size_t)batch;
-    T *d = nullptr;
-    hipStream_t s = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e != hipSuccess) return hip_err(e, "hipStreamCreate");
-    e = hipMallocAsync((void **)&d, per * (nin + nout) * sizeof(T), s);
-    if (e != hipSuccess) { (void)hipStreamDestroy(s); return hip_err(e, "hipMallocAsync"); }
-    for (int k = 0; k < nin && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(d + k * per, in[k], per * sizeof(T), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) rc = launch(d, d + nin * per, s);
-    else rc = hip_err(e, "hipMemcpyAsync H2D");
-    for (int k = 0; k < nout && rc == RB_OK; ++k) {
-        e = hipMemcpyAsync(out[k], d + (nin + k) * per, per * sizeof(T), hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) rc = hip_err(e, "hipMemcpyAsync D2H");
-    }
-    (void)hipFreeAsync(d, s);
-    e = hipStreamSynchronize(s);
-    if (rc == RB_OK && e != hipSuccess) rc = hip_err(e, "hipStreamSynchronize");
-    (void)hipStreamDestroy(s);
-    return rc;
-}
-// Blocking host-pointer forms: SoA rows x[j * batch + b] in host memory, copied to a scratch
-// device buffer on a private stream, evaluated by the batched kernels, copied back.
-template <typename T>
-int rnea_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *tau, int64_t batch) {
-    const T *in[3] = {q, qd, qdd};
-    T *out[1] = {tau};
-    return host_batch<T>(mb, in, 3, out, 1, batch, [&](T *d, T *o, hipStream_t s) {
-        const size_t per = (size_t)mb->model.n * (size_t)batch;
-        return rnea_batch<T>(mb, d, d + per, d + 2 * per, o, batch, batch, s);
-    });
-}
-template <typename T>
-int fd_host(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, int64_t batch) {
-    const T *in[3] = {q, qd, tau};
-    T *out[1] = {qdd};
-    return host_batch<T>(mb, in, 3, out, 1, batch, [&](T *d, T *o, hipStream_t s) {
-        const size_t per = (size_t)mb->model.n * (size_t)batch;
-        return fd_batch<T>(mb, d, d + per, d + 2 * per, o, batch, batch, s);
-    });
-}
-template <typename T>
-int idfd_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, const T *tau_in, T *tau, T *qdd_out,
-              int64_t batch) {
-    const T *in[4] = {q, qd, qdd, tau_in};
-    T *out[2] = {tau, qdd_out};
-    return host_batch<T>(mb, in, 4, out, 2, batch, [&](T *d, T *o, hipStream_t s) {
-        const size_t per = (size_t)mb->model.n * (size_t)batch;
-        return idfd_batch<T>(mb, d, d + per, d + 2 * per, d + 3 * per, o, o + per, batch, batch, s);
-    });
-}
-
-// The derivative entry points' blocking host form: nin [n][batch] inputs; outputs of rows[k] rows
-// each ([rows][batch]), a NULL one skipped.  check() runs after the handle / batch checks and
-// before any device work; launch(d_in, d_out[], stream) gets the device arrays (NULL for a skipped
-// output).
-template <typename T, int NOUT, typename Check, typename Launch>
-int host_deriv_batch(const Multibody *mb, const T *const *in, int nin, T *const *out, const int64_t *rows, int64_t batch,
-                     Check check, Launch launch) {
-    int rc = check_batch(mb, batch, batch);
-    if (rc) return rc;
-    if (batch == 0) return RB_OK;
+    for (const T *p : in)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    for (const T *p : out)
+        if (!p && !null_outputs) return set_err(RB_ERR_NULL, "NULL array");
     if ((rc = check())) return rc;
     const size_t per = (size_t)mb->model.n * (size_t)batch;
-    size_t total = per * nin;
-    size_t at[NOUT];
+    size_t total = per * NIN, at[NOUT];
     for (int k = 0; k < NOUT; ++k) {
         at[k] = total;
         if (out[k]) total += (size_t)rows[k] * (size_t)batch;
@@ -755,11 +603,12 @@ int host_deriv_batch(const Multibody *mb, const T *const *in, int nin, T *const 
     if (e != hipSuccess) return hip_err(e, "hipStreamCreate");
     e = hipMallocAsync((void **)&d, total * sizeof(T), s);
     if (e != hipSuccess) { (void)hipStreamDestroy(s); return hip_err(e, "hipMallocAsync"); }
-    for (int k = 0; k < nin && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(d + k * per, in[k], per * sizeof(T), hipMemcpyHostToDevice, s);
-    T *dout[NOUT];
+    T *din[NIN], *dout[NOUT];
+    for (int k = 0; k < NIN; ++k) din[k] = d + k * per;
     for (int k = 0; k < NOUT; ++k) dout[k] = out[k] ? d + at[k] : nullptr;
-    if (e == hipSuccess) rc = launch(d, dout, s);
+    for (int k = 0; k < NIN && e == hipSuccess; ++k)
+        e = hipMemcpyAsync(din[k], in[k], per * sizeof(T), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) rc = launch(din, dout, s);
     else rc = hip_err(e, "hipMemcpyAsync H2D");
     for (int k = 0; k < NOUT && rc == RB_OK; ++k) {
         if (!out[k]) continue;
@@ -773,34 +622,52 @@ int host_deriv_batch(const Multibody *mb, const T *const *in, int nin, T *const 
     return rc;
 }
 
+const auto no_check = [] { return (int)RB_OK; };
+
+template <typename T>
+int rnea_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *tau, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call<T, 3, 1>(mb, {q, qd, qdd}, {tau}, {n}, false, batch, no_check, [&](T **i, T **o, hipStream_t s) {
+        return rnea_batch<T>(mb, i[0], i[1], i[2], o[0], batch, batch, s);
+    });
+}
+template <typename T>
+int fd_host(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call<T, 3, 1>(mb, {q, qd, tau}, {qdd}, {n}, false, batch, no_check, [&](T **i, T **o, hipStream_t s) {
+        return fd_batch<T>(mb, i[0], i[1], i[2], o[0], batch, batch, s);
+    });
+}
+template <typename T>
+int idfd_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, const T *tau_in, T *tau, T *qdd_out,
+              int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call<T, 4, 2>(mb, {q, qd, qdd, tau_in}, {tau, qdd_out}, {n, n}, false, batch, no_check,
+                              [&](T **i, T **o, hipStream_t s) {
+        return idfd_batch<T>(mb, i[0], i[1], i[2], i[3], o[0], o[1], batch, batch, s);
+    });
+}
+
 template <typename T>
 int rnea_deriv_host(const Multibody *mb, const T *q, const T *qd, const T *qdd, T *dq, T *dqd, int64_t batch) {
-    const T *in[3] = {q, qd, qdd};
-    T *out[2] = {dq, dqd};
     const int64_t nn = mb ? (int64_t)mb->model.n * mb->model.n : 0;
-    const int64_t rows[2] = {nn, nn};
-    return host_deriv_batch<T, 2>(
-        mb, in, 3, out, rows, batch,
+    return host_call<T, 3, 2>(
+        mb, {q, qd, qdd}, {dq, dqd}, {nn, nn}, true, batch,
         [&] { return deriv_args_ok<T>(mb, rbamd::JitKind::RneaDeriv, "rnea_deriv", {q, qd, qdd}, {dq, dqd}); },
-        [&](T *d, T *const *o, hipStream_t s) {
-            const size_t per = (size_t)mb->model.n * (size_t)batch;
-            return rnea_deriv_batch<T>(mb, d, d + per, d + 2 * per, o[0], o[1], batch, batch, s);
+        [&](T **i, T **o, hipStream_t s) {
+            return rnea_deriv_batch<T>(mb, i[0], i[1], i[2], o[0], o[1], batch, batch, s);
         });
 }
 
 template <typename T>
 int fd_deriv_host(const Multibody *mb, const T *q, const T *qd, const T *tau, T *qdd, T *dq, T *dqd, T *dtau,
                   int64_t batch) {
-    const T *in[3] = {q, qd, tau};
-    T *out[4] = {qdd, dq, dqd, dtau};
-    const int64_t n = mb ? mb->model.n : 0;
-    const int64_t rows[4] = {n, n * n, n * n, n * n};
-    return host_deriv_batch<T, 4>(
-        mb, in, 3, out, rows, batch,
+    const int64_t n = mb ? mb->model.n : 0, nn = n * n;
+    return host_call<T, 3, 4>(
+        mb, {q, qd, tau}, {qdd, dq, dqd, dtau}, {n, nn, nn, nn}, true, batch,
         [&] { return deriv_args_ok<T>(mb, rbamd::JitKind::FdDeriv, "fd_deriv", {q, qd, tau}, {qdd, dq, dqd, dtau}); },
-        [&](T *d, T *const *o, hipStream_t s) {
-            const size_t per = (size_t)mb->model.n * (size_t)batch;
-            return fd_deriv_batch<T>(mb, d, d + per, d + 2 * per, o[0], o[1], o[2], o[3], batch, batch, s);
+        [&](T **i, T **o, hipStream_t s) {
+            return fd_deriv_batch<T>(mb, i[0], i[1], i[2], o[0], o[1], o[2], o[3], batch, batch, s);
         });
 }
 }  // namespace
@@ -846,23 +713,7 @@ Multibody *multibody_new(void) {
     return new_from_text(std::string(kFr3Urdf));
 }
 
-void multibody_free(Multibody *mb) {
-    if (!mb) return;
-    int cur = 0;
-    bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    for (auto &kv : mb->dev) {
-        if (hipSetDevice(kv.first) != hipSuccess) continue;
-        if (kv.second.f32) (void)hipFree(kv.second.f32);
-        if (kv.second.f64) (void)hipFree(kv.second.f64);
-    }
-    for (auto &kv : mb->jit) {
-        if (!kv.second.module) continue;
-        if (hipSetDevice(mb->jit_device[kv.first]) != hipSuccess) continue;
-        (void)hipModuleUnload(kv.second.module);
-    }
-    if (have_cur) (void)hipSetDevice(cur);
-    delete mb;
-}
+void multibody_free(Multibody *mb) { delete mb; }  // ~DeviceCache frees what it put on the devices
 
 double *multibody_rnea(const Multibody *mb, const double *q, const double *dq, const double *ddq) {
     const size_t n = mb ? (size_t)mb->model.n : 0;
@@ -1015,9 +866,7 @@ std::string shaped_source(const Multibody *mb, int kind, bool f64, int64_t batch
 }
 
 void note_jit_errors(const Multibody *mb) {
-    std::lock_guard<std::mutex> lk(mb->mu);
-    for (auto &kv : mb->jit)
-        if (!kv.second.error.empty()) g_last_error = kv.second.error;
+    for (std::string &err : mb->cache.jit_errors()) g_last_error = std::move(err);
 }
 }  // namespace
 

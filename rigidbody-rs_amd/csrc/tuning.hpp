@@ -116,7 +116,7 @@ bool tuning_experimental();
 int tuning_set(const char *key, int value);
 
 // Advanced twice by every successful tuning_set (odd while the write is in progress, even
-// otherwise): per-launch caches keyed on the tuning state (capi.cpp jit_get's fast path)
+// otherwise): per-launch caches keyed on the tuning state (the fast path of device_cache.cpp DeviceCache::kernel)
 // compare it instead of rebuilding their string keys.
 unsigned tuning_generation();
 // The current generation once no rb_set_tuning write is in progress (an even sequence count).

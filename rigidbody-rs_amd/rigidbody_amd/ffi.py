@@ -36,94 +36,78 @@ if not os.path.exists(LIB_PATH):
 
 _lib = ctypes.CDLL(LIB_PATH)
 
+_int, _uint, _i64, _u64, _size = ctypes.c_int, ctypes.c_uint, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
+_dbl, _str, _vp = ctypes.c_double, ctypes.c_char_p, ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)
-_vp = ctypes.c_void_p
-_i64 = ctypes.c_int64
+_ip = ctypes.POINTER(ctypes.c_int)
 
 # exported symbols declared in include/*.h (tests check the list against the headers)
 REFERENCE_SYMBOLS = ["multibody_new", "multibody_fwd_kin", "multibody_jac", "multibody_rnea",
                      "multibody_crba", "multibody_free"]
-
-
-def _sig(name, restype, argtypes):
-    f = getattr(_lib, name)
-    f.restype = restype
-    f.argtypes = argtypes
-    return f
-
-
-_sig("multibody_new", _vp, [])
-_sig("multibody_free", None, [_vp])
-for _n in ("multibody_fwd_kin", "multibody_jac", "multibody_crba"):
-    _sig(_n, _dp, [_vp, _dp])
-_sig("multibody_rnea", _dp, [_vp, _dp, _dp, _dp])
-_sig("multibody_new_from_urdf", _vp, [ctypes.c_char_p])
-_sig("multibody_new_from_urdf_string", _vp, [ctypes.c_char_p, ctypes.c_size_t])
-_sig("multibody_new_from_urdf_ex", _vp, [ctypes.c_char_p, ctypes.c_uint])
-_sig("multibody_new_from_urdf_string_ex", _vp, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint])
-_sig("multibody_flags", ctypes.c_uint, [_vp])
-_sig("multibody_blob_size", _i64, [_vp])
-_sig("multibody_export_blob", ctypes.c_int, [_vp, _dp, _i64])
-_sig("multibody_new_from_blob", _vp, [_dp, _i64])
-_sig("multibody_dof", ctypes.c_int, [_vp])
-_sig("multibody_total_mass", ctypes.c_double, [_vp])
-_sig("multibody_limits", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp])
-_sig("multibody_supported_dofs", ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int])
-_sig("multibody_upload", ctypes.c_int, [_vp])
-_sig("multibody_result_free", None, [_dp])
-_sig("rb_last_error", ctypes.c_char_p, [])
-_sig("rb_version", ctypes.c_char_p, [])
-for _t in ("f32", "f64"):
-    _sig(f"multibody_rnea_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
-    _sig(f"multibody_fd_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
-    _sig(f"multibody_crba_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp])
-    _sig(f"rb_fill_uniform_{_t}", ctypes.c_int, [_vp, ctypes.c_int, _i64, _i64, _dp, _dp, ctypes.c_uint64, _vp])
-    _sig(f"multibody_rnea_fd_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
-    _sig(f"multibody_rnea_fd_batch_tiled_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp])
-_sig("multibody_fwd_kin_batch_f64", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp])
-_sig("multibody_fwd_kin_batch_f32", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp])
-_sig("multibody_jac_batch_f32", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp])
-_sig("multibody_jac_batch_f64", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp])
-_sig("multibody_rnea_batch_host_f64", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _i64])
-_fp = ctypes.POINTER(ctypes.c_float)
-_sig("multibody_rnea_batch_host_f32", ctypes.c_int, [_vp, _fp, _fp, _fp, _fp, _i64])
-_sig("multibody_fd_batch_host_f32", ctypes.c_int, [_vp, _fp, _fp, _fp, _fp, _i64])
-_sig("multibody_rnea_kernel_path", ctypes.c_int, [_vp, ctypes.c_int])
-_sig("multibody_single_config_path", ctypes.c_int, [_vp])
-_sig("multibody_kernel_path", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int])
-_sig("multibody_kernel_path_ex", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int])
-_sig("multibody_kernel_form_ex", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int])
-_sig("multibody_jit_source", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, _i64])
-_sig("multibody_jit_compile", _i64, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p])
-_sig("multibody_jit_source_ex", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_char_p, _i64])
-_sig("multibody_jit_compile_ex", _i64, [_vp, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_char_p])
 KINDS = {"rnea": 0, "fd": 1, "crba": 2, "rollout": 3, "fwd_kin": 4, "jac": 5, "rnea_fd": 6, "rnea_deriv": 7,
          "fd_deriv": 8}
-for _t in ("f32", "f64"):
-    _sig(f"multibody_rnea_deriv_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
-    _sig(f"multibody_fd_deriv_batch_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp])
-    _sig(f"multibody_rnea_deriv_batch_host_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64])
-    _sig(f"multibody_fd_deriv_batch_host_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64])
-_sig("multibody_rnea_deriv", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp])
-_sig("multibody_fd_deriv", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp])
 GENERAL_AXES, URDF_TREE, FLOATING_BASE = 1, 2, 4  # rigidbody_batch.h RB_MODEL_*
-_ip = ctypes.POINTER(ctypes.c_int)
-_sig("multibody_topology", ctypes.c_int, [_vp, _ip, _ip])
-for _t in ("f32", "f64"):
-    _sig(f"multibody_rollout_batch_{_t}", ctypes.c_int,
-         [_vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int, _vp, _i64, _i64, _vp])
-_sig("rb_set_tuning", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int])
-_sig("multibody_fd_batch_host_f64", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _i64])
-_sig("multibody_rnea_fd_batch_host_f64", ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _i64])
-_sig("multibody_rnea_fd_batch_host_f32", ctypes.c_int, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i64])
-for _t in ("f32", "f64"):
-    _sig(f"multibody_rnea_batch_tiled_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp])
-    _sig(f"multibody_fd_batch_tiled_{_t}", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp])
-    _sig(f"rb_to_tiled_{_t}", ctypes.c_int, [_vp, _i64, _vp, ctypes.c_int, _i64, _vp])
-    for _k in ("crba", "fwd_kin", "jac"):
-        _sig(f"multibody_{_k}_batch_tiled_{_t}", ctypes.c_int, [_vp, _vp, _vp, _i64, _vp])
-    _sig(f"rb_from_tiled_{_t}", ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, _i64, _vp])
 TILE = 256  # configurations per tile of the tiled layout (rigidbody_batch.h)
+
+# name -> (restype, argtypes); the handle and device / host arrays are void pointers
+_SIGNATURES = {
+    # the reference ABI (rigidbody.h)
+    "multibody_new": (_vp, []),
+    "multibody_free": (None, [_vp]),
+    "multibody_fwd_kin": (_dp, [_vp, _dp]),
+    "multibody_jac": (_dp, [_vp, _dp]),
+    "multibody_crba": (_dp, [_vp, _dp]),
+    "multibody_rnea": (_dp, [_vp, _dp, _dp, _dp]),
+    # model construction and properties
+    "multibody_new_from_urdf": (_vp, [_str]),
+    "multibody_new_from_urdf_string": (_vp, [_str, _size]),
+    "multibody_new_from_urdf_ex": (_vp, [_str, _uint]),
+    "multibody_new_from_urdf_string_ex": (_vp, [_str, _size, _uint]),
+    "multibody_new_from_blob": (_vp, [_dp, _i64]),
+    "multibody_export_blob": (_int, [_vp, _dp, _i64]),
+    "multibody_blob_size": (_i64, [_vp]),
+    "multibody_flags": (_uint, [_vp]),
+    "multibody_dof": (_int, [_vp]),
+    "multibody_total_mass": (_dbl, [_vp]),
+    "multibody_limits": (_int, [_vp, _dp, _dp, _dp, _dp]),
+    "multibody_topology": (_int, [_vp, _ip, _ip]),
+    "multibody_supported_dofs": (_int, [_ip, _int]),
+    "multibody_upload": (_int, [_vp]),
+    # kernel inspection: (handle, kind, f64[, batch, tiled], ...)
+    "multibody_rnea_kernel_path": (_int, [_vp, _int]),
+    "multibody_single_config_path": (_int, [_vp]),
+    "multibody_kernel_path": (_int, [_vp, _int, _int]),
+    "multibody_kernel_path_ex": (_int, [_vp, _int, _int, _i64, _int]),
+    "multibody_kernel_form_ex": (_int, [_vp, _int, _int, _i64, _int]),
+    "multibody_jit_source": (_int, [_vp, _int, _int, _str, _i64]),
+    "multibody_jit_source_ex": (_int, [_vp, _int, _int, _i64, _int, _str, _i64]),
+    "multibody_jit_compile": (_i64, [_vp, _int, _int, _str]),
+    "multibody_jit_compile_ex": (_i64, [_vp, _int, _int, _i64, _int, _str]),
+    # process-wide
+    "multibody_result_free": (None, [_dp]),
+    "rb_last_error": (_str, []),
+    "rb_version": (_str, []),
+    "rb_set_tuning": (_int, [_str, _int]),
+    # one configuration, fp64, on the calling thread
+    "multibody_rnea_deriv": (_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "multibody_fd_deriv": (_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+}
+# batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
+_ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7}
+for _t in ("f32", "f64"):
+    for _k, _n in _ARRAYS.items():
+        _SIGNATURES[f"multibody_{_k}_batch_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _i64, _vp])
+        if not _k.endswith("_deriv"):
+            _SIGNATURES[f"multibody_{_k}_batch_tiled_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _vp])
+        if _k not in ("crba", "fwd_kin", "jac"):
+            _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
+    _SIGNATURES[f"multibody_rollout_batch_{_t}"] = (_int, [_vp, _vp, _vp, _vp, _dbl, _int, _vp, _i64, _i64, _vp])
+    _SIGNATURES[f"rb_fill_uniform_{_t}"] = (_int, [_vp, _int, _i64, _i64, _dp, _dp, _u64, _vp])
+    _SIGNATURES[f"rb_to_tiled_{_t}"] = (_int, [_vp, _i64, _vp, _int, _i64, _vp])
+    _SIGNATURES[f"rb_from_tiled_{_t}"] = (_int, [_vp, _vp, _i64, _int, _i64, _vp])
+for _name, (_res, _args) in _SIGNATURES.items():
+    _f = getattr(_lib, _name)
+    _f.restype, _f.argtypes = _res, _args
 
 
 class RigidBodyError(RuntimeError):
@@ -238,14 +222,6 @@ def _same_ld(ts):
     if len(lds) != 1:
         raise ValueError("all [n, B] arrays of one call must share the leading dimension")
     return lds.pop()
-
-
-def _kin_out(out, rows, q):
-    """Output of fwd_kin / jac batches: [rows, B] of q's dtype with the input's leading dimension."""
-    B = q.shape[1]
-    if not isinstance(out, torch.Tensor) or out.dtype != q.dtype or tuple(out.shape) != (rows, B) or \
-            (B > 1 and (out.stride(1) != 1 or out.stride(0) != _ld(q))):
-        raise ValueError(f"out must be a {q.dtype} [{rows}, {B}] tensor with the input's leading dimension")
 
 
 class Multibody:
@@ -415,9 +391,31 @@ class Multibody:
         return (qdd, *(o.reshape(self.n, self.n).T.copy() for o in outs))
 
     # ------------------------------------------------------- batched, device [n, B]
-    def _mat_out(self, q):
-        """An [n*n, B] matrix output with q's leading dimension."""
-        return torch.empty((self.n * self.n, _ld(q)), dtype=q.dtype, device=q.device)[:, :q.shape[1]]
+    def _soa_call(self, kind, ins, outs, stream):
+        """multibody_<kind>_batch_f32 / _f64 on [rows, B] CUDA tensors.  ins: (tensor, name) pairs,
+        each [n, B]; the first sets the dtype and B.  outs: (tensor, name, rows) triples: None is
+        allocated with the inputs' leading dimension, False is not wanted (passed as NULL), a
+        tensor is checked like an input.  Returns the outputs in order (False where skipped)."""
+        q = _soa(ins[0][0], self.n, ins[0][1])
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"{ins[0][1]} has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        ts = [q] + [_soa(t, self.n, name, q.dtype, B) for t, name in ins[1:]]
+        res = []
+        for o, name, rows in outs:
+            if o is None:
+                o = torch.empty((rows, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
+            elif o is not False:
+                _soa(o, rows, name, q.dtype, B)
+            res.append(o)
+        live = ts + [o for o in res if o is not False]
+        ld = _same_ld(live)
+        dev = _one_device(live)
+        fn = getattr(_lib, f"multibody_{kind}_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, *[t.data_ptr() for t in ts], *[None if o is False else o.data_ptr() for o in res],
+                      B, ld, _stream_ptr(stream, dev)), f"{kind}_batch")
+        return res
 
     def rnea_deriv_batch(self, q, qd, qdd, want=("q", "qd"), stream=None):
         """multibody_rnea_deriv_batch_*: the derivatives of tau = rnea(q, qd, qdd) named in `want`
@@ -427,152 +425,87 @@ class Multibody:
         want = tuple(want)
         if not want or any(w not in ("q", "qd") for w in want) or len(set(want)) != len(want):
             raise ValueError('want must name "q" and / or "qd"')
-        q = _soa(q, self.n, "q")
-        B = q.shape[1]
-        qd = _soa(qd, self.n, "qd", q.dtype, B)
-        qdd = _soa(qdd, self.n, "qdd", q.dtype, B)
-        ld = _same_ld((q, qd, qdd))
-        dev = _one_device((q, qd, qdd))
-        outs = {w: self._mat_out(q) for w in want}
-        ptr = {w: (outs[w].data_ptr() if w in outs else None) for w in ("q", "qd")}
-        fn = getattr(_lib, f"multibody_rnea_deriv_batch_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), ptr["q"], ptr["qd"], B, ld,
-                      _stream_ptr(stream, dev)), "rnea_deriv_batch")
-        return tuple(outs[w] for w in want)
+        outs = self._soa_call("rnea_deriv", [(q, "q"), (qd, "qd"), (qdd, "qdd")],
+                              [(None if w in want else False, "dtau_d" + w, self.n * self.n) for w in ("q", "qd")],
+                              stream)
+        return tuple(outs[("q", "qd").index(w)] for w in want)
 
     def fd_deriv_batch(self, q, qd, tau, stream=None):
         """multibody_fd_deriv_batch_*: (qdd [n, B], dqdd_dq, dqdd_dqd, dqdd_dtau [n*n, B]) of
         qdd = fd(q, qd, tau) in one launch; qdd is fd_batch's, bit for bit."""
-        q = _soa(q, self.n, "q")
-        B = q.shape[1]
-        qd = _soa(qd, self.n, "qd", q.dtype, B)
-        tau = _soa(tau, self.n, "tau", q.dtype, B)
-        ld = _same_ld((q, qd, tau))
-        dev = _one_device((q, qd, tau))
-        qdd = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
-        mats = [self._mat_out(q) for _ in range(3)]
-        fn = getattr(_lib, f"multibody_fd_deriv_batch_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), qdd.data_ptr(),
-                      *[m.data_ptr() for m in mats], B, ld, _stream_ptr(stream, dev)), "fd_deriv_batch")
-        return (qdd, *mats)
+        nn = self.n * self.n
+        return tuple(self._soa_call("fd_deriv", [(q, "q"), (qd, "qd"), (tau, "tau")],
+                                    [(None, "qdd", self.n), (None, "dqdd_dq", nn), (None, "dqdd_dqd", nn),
+                                     (None, "dqdd_dtau", nn)], stream))
 
     def rnea_batch(self, q, qd, qdd, out=None, stream=None):
-        q = _soa(q, self.n, "q")
-        B = q.shape[1]
-        qd = _soa(qd, self.n, "qd", q.dtype, B)
-        qdd = _soa(qdd, self.n, "qdd", q.dtype, B)
-        if out is None:
-            out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
-        _soa(out, self.n, "tau", q.dtype, B)
-        ld = _same_ld((q, qd, qdd, out))
-        dev = _one_device((q, qd, qdd, out))
-        fn = getattr(_lib, f"multibody_rnea_batch_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), out.data_ptr(), B, ld,
-                      _stream_ptr(stream, dev)), "rnea_batch")
-        return out
+        return self._soa_call("rnea", [(q, "q"), (qd, "qd"), (qdd, "qdd")], [(out, "tau", self.n)], stream)[0]
 
     def fd_batch(self, q, qd, tau, out=None, stream=None):
-        q = _soa(q, self.n, "q")
-        B = q.shape[1]
-        qd = _soa(qd, self.n, "qd", q.dtype, B)
-        tau = _soa(tau, self.n, "tau", q.dtype, B)
-        if out is None:
-            out = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device)
-        _soa(out, self.n, "qdd", q.dtype, B)
-        ld = _same_ld((q, qd, tau, out))
-        dev = _one_device((q, qd, tau, out))
-        fn = getattr(_lib, f"multibody_fd_batch_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), out.data_ptr(), B, ld,
-                      _stream_ptr(stream, dev)), "fd_batch")
-        return out
+        return self._soa_call("fd", [(q, "q"), (qd, "qd"), (tau, "tau")], [(out, "qdd", self.n)], stream)[0]
 
     def rnea_fd_batch(self, q, qd, qdd, tau_in, tau=None, qdd_out=None, stream=None):
         """multibody_rnea_fd_batch_*: (tau = rnea(q, qd, qdd), qdd_out = fd(q, qd, tau_in)) in one
         launch for mass-matrix models (two kernels otherwise); [n, B] CUDA tensors."""
-        q = _soa(q, self.n, "q")
-        B = q.shape[1]
-        ins = [q] + [_soa(x, self.n, k, q.dtype, B) for x, k in ((qd, "qd"), (qdd, "qdd"), (tau_in, "tau_in"))]
-        outs = []
-        for o, k in ((tau, "tau"), (qdd_out, "qdd_out")):
-            o = torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device) if o is None else o
-            outs.append(_soa(o, self.n, k, q.dtype, B))
-        ld = _same_ld(ins + outs)
-        dev = _one_device(ins + outs)
-        fn = getattr(_lib, f"multibody_rnea_fd_batch_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, *[t.data_ptr() for t in ins + outs], B, ld, _stream_ptr(stream, dev)), "rnea_fd_batch")
-        return outs[0], outs[1]
+        return tuple(self._soa_call("rnea_fd", [(q, "q"), (qd, "qd"), (qdd, "qdd"), (tau_in, "tau_in")],
+                                    [(tau, "tau", self.n), (qdd_out, "qdd_out", self.n)], stream))
 
-    def rnea_fd_batch_tiled(self, q, qd, qdd, tau_in, B, tau=None, qdd_out=None, stream=None):
-        """The same on tiled [ceil(B/256), n, 256] tensors (multibody_rnea_fd_batch_tiled_*)."""
-        q = self._tiled(q, "q", B)
-        ins = [q] + [self._tiled(x, k, B, q.dtype) for x, k in ((qd, "qd"), (qdd, "qdd"), (tau_in, "tau_in"))]
-        outs = [torch.empty_like(q) if o is None else self._tiled(o, k, B, q.dtype)
-                for o, k in ((tau, "tau"), (qdd_out, "qdd_out"))]
-        dev = _one_device(ins + outs)
-        fn = getattr(_lib, f"multibody_rnea_fd_batch_tiled_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, *[t.data_ptr() for t in ins + outs], B, _stream_ptr(stream, dev)),
-                   "rnea_fd_batch_tiled")
-        return outs[0], outs[1]
+    def crba_batch(self, q, out=None, stream=None):
+        return self._soa_call("crba", [(q, "q")], [(out, "out", self.n * self.n)], stream)[0]
+
+    def fwd_kin_batch(self, q, out=None, stream=None):
+        return self._soa_call("fwd_kin", [(q, "q")], [(out, "out", 3)], stream)[0]
+
+    def jac_batch(self, q, out=None, stream=None):
+        return self._soa_call("jac", [(q, "q")], [(out, "out", 6 * self.n)], stream)[0]
 
     # ---- tiled layout [ceil(B/256), n, 256] (rigidbody_batch.h) ----------------------
-    def _tiled(self, t, name, B, dtype=None):
+    def _tiled(self, t, name, B, rows, dtype=None):
         T = (B + TILE - 1) // TILE
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError(f"{name} must be a CUDA (HIP) torch tensor of shape [tiles, n, 256]")
-        if tuple(t.shape) != (T, self.n, TILE) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous [{T}, {self.n}, {TILE}] tensor for batch {B}")
+            raise TypeError(f"{name} must be a CUDA (HIP) torch tensor of shape [tiles, {rows}, 256]")
+        if tuple(t.shape) != (T, rows, TILE) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [{T}, {rows}, {TILE}] tensor for batch {B}")
         if dtype is not None and t.dtype != dtype:
             raise TypeError(f"{name} has dtype {t.dtype}, expected {dtype}")
         return t
 
-    def _tiled_call(self, kind, a, b, c, B, out, stream):
-        a = self._tiled(a, "arg0", B)
-        b, c = self._tiled(b, "arg1", B, a.dtype), self._tiled(c, "arg2", B, a.dtype)
-        out = torch.empty_like(a) if out is None else self._tiled(out, "out", B, a.dtype)
-        dev = _one_device((a, b, c, out))
-        fn = getattr(_lib, f"multibody_{kind}_batch_tiled_{_TORCH_SUFFIX[a.dtype]}")
+    def _tiled_call(self, kind, ins, outs, B, stream):
+        """multibody_<kind>_batch_tiled_f32 / _f64: as _soa_call on tiled tensors -- ins
+        [ceil(B/256), n, 256], outs (tensor or None, name, rows) [ceil(B/256), rows, 256]."""
+        q = self._tiled(ins[0][0], ins[0][1], B, self.n)
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"{ins[0][1]} has dtype {q.dtype}, expected float32 or float64")
+        ts = [q] + [self._tiled(t, name, B, self.n, q.dtype) for t, name in ins[1:]]
+        res = [torch.empty((q.shape[0], rows, TILE), dtype=q.dtype, device=q.device) if o is None
+               else self._tiled(o, name, B, rows, q.dtype) for o, name, rows in outs]
+        dev = _one_device(ts + res)
+        fn = getattr(_lib, f"multibody_{kind}_batch_tiled_{_TORCH_SUFFIX[q.dtype]}")
         with torch.cuda.device(dev):
-            _check(fn(self._h, a.data_ptr(), b.data_ptr(), c.data_ptr(), out.data_ptr(), B,
-                      _stream_ptr(stream, dev)), f"{kind}_batch_tiled")
-        return out
+            _check(fn(self._h, *[t.data_ptr() for t in ts + res], B, _stream_ptr(stream, dev)), f"{kind}_batch_tiled")
+        return res
 
     def rnea_batch_tiled(self, q, qd, qdd, B, out=None, stream=None):
         """RNEA on tiled [ceil(B/256), n, 256] tensors (see to_tiled)."""
-        return self._tiled_call("rnea", q, qd, qdd, B, out, stream)
+        return self._tiled_call("rnea", [(q, "q"), (qd, "qd"), (qdd, "qdd")], [(out, "out", self.n)], B, stream)[0]
 
     def fd_batch_tiled(self, q, qd, tau, B, out=None, stream=None):
-        return self._tiled_call("fd", q, qd, tau, B, out, stream)
+        return self._tiled_call("fd", [(q, "q"), (qd, "qd"), (tau, "tau")], [(out, "out", self.n)], B, stream)[0]
 
-    def _q_tiled(self, kind, rows, q, B, out, stream):
-        q = self._tiled(q, "q", B)
-        if q.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
-        shape = ((B + TILE - 1) // TILE, rows, TILE)
-        if out is None:
-            out = torch.empty(shape, dtype=q.dtype, device=q.device)
-        elif tuple(out.shape) != shape or out.dtype != q.dtype or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous {list(shape)} tensor of q's dtype")
-        dev = _one_device((q, out))
-        fn = getattr(_lib, f"multibody_{kind}_batch_tiled_{_TORCH_SUFFIX[q.dtype]}")
-        with torch.cuda.device(dev):
-            _check(fn(self._h, q.data_ptr(), out.data_ptr(), B, _stream_ptr(stream, dev)), f"{kind}_batch_tiled")
-        return out
+    def rnea_fd_batch_tiled(self, q, qd, qdd, tau_in, B, tau=None, qdd_out=None, stream=None):
+        """rnea_fd_batch on tiled [ceil(B/256), n, 256] tensors (multibody_rnea_fd_batch_tiled_*)."""
+        return tuple(self._tiled_call("rnea_fd", [(q, "q"), (qd, "qd"), (qdd, "qdd"), (tau_in, "tau_in")],
+                                      [(tau, "tau", self.n), (qdd_out, "qdd_out", self.n)], B, stream))
 
     def crba_batch_tiled(self, q, B, out=None, stream=None):
         """Mass matrices on the tiled layout: q [ceil(B/256), n, 256] -> [ceil(B/256), n*n, 256]."""
-        return self._q_tiled("crba", self.n * self.n, q, B, out, stream)
+        return self._tiled_call("crba", [(q, "q")], [(out, "out", self.n * self.n)], B, stream)[0]
 
     def fwd_kin_batch_tiled(self, q, B, out=None, stream=None):
-        return self._q_tiled("fwd_kin", 3, q, B, out, stream)
+        return self._tiled_call("fwd_kin", [(q, "q")], [(out, "out", 3)], B, stream)[0]
 
     def jac_batch_tiled(self, q, B, out=None, stream=None):
-        return self._q_tiled("jac", 6 * self.n, q, B, out, stream)
+        return self._tiled_call("jac", [(q, "q")], [(out, "out", 6 * self.n)], B, stream)[0]
 
     def rollout_batch(self, q, qd, tau_seq, dt, traj=False, stream=None):
         """K fused forward-dynamics + semi-implicit Euler steps, in place on q and qd
@@ -598,97 +531,38 @@ class Multibody:
                    "rollout_batch")
         return tr
 
-    def crba_batch(self, q, out=None, stream=None):
-        q = _soa(q, self.n, "q")
-        B = q.shape[1]
-        if out is None:
-            out = torch.empty((self.n * self.n, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
-        fn = getattr(_lib, f"multibody_crba_batch_{_TORCH_SUFFIX[q.dtype]}")
-        if out.shape != (self.n * self.n, B) or (B > 1 and out.stride(0) != _ld(q)):
-            raise ValueError("out must be [n*n, B] with the inputs' leading dimension")
-        dev = _one_device((q, out))
-        with torch.cuda.device(dev):
-            _check(fn(self._h, q.data_ptr(), out.data_ptr(), B, _ld(q), _stream_ptr(stream, dev)), "crba_batch")
-        return out
-
-    def fwd_kin_batch(self, q, out=None, stream=None):
-        q = _soa(q, self.n, "q")
-        if q.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
-        B = q.shape[1]
-        if out is None:
-            out = torch.empty((3, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
-        _kin_out(out, 3, q)
-        dev = _one_device((q, out))
-        with torch.cuda.device(dev):
-            fn = _lib.multibody_fwd_kin_batch_f64 if q.dtype == torch.float64 else _lib.multibody_fwd_kin_batch_f32
-            _check(fn(self._h, q.data_ptr(), out.data_ptr(), B, _ld(q), _stream_ptr(stream, dev)), "fwd_kin_batch")
-        return out
-
-    def jac_batch(self, q, out=None, stream=None):
-        q = _soa(q, self.n, "q")
-        if q.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
-        B = q.shape[1]
-        if out is None:
-            out = torch.empty((6 * self.n, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
-        _kin_out(out, 6 * self.n, q)
-        dev = _one_device((q, out))
-        with torch.cuda.device(dev):
-            fn = _lib.multibody_jac_batch_f64 if q.dtype == torch.float64 else _lib.multibody_jac_batch_f32
-            _check(fn(self._h, q.data_ptr(), out.data_ptr(), B, _ld(q), _stream_ptr(stream, dev)), "jac_batch")
-        return out
-
     # -------------------------------------------------------- batched, host [n, B]
+    def _host_call(self, kind, ins, out_rows, dtype):
+        """multibody_<kind>_batch_host_f64 / _f32 (blocking): `ins` as [n, B] numpy arrays of
+        `dtype`; returns one new [rows, B] array per entry of out_rows."""
+        arrs = _host_soa(ins, self.n, dtype)
+        B = arrs[0].shape[1]
+        outs = [np.empty((rows, B), dtype=arrs[0].dtype) for rows in out_rows]
+        fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in arrs + outs], B), f"{kind}_batch_host")
+        return outs
+
     def rnea_batch_host(self, q, qd, qdd, dtype=np.float64):
         """Blocking host form: multibody_rnea_batch_host_f64 (default: fp64, the reference's Real,
         whatever the inputs' dtype) or _f32 with dtype=np.float32."""
-        return self._host_call("rnea", (q, qd, qdd), dtype)
+        return self._host_call("rnea", (q, qd, qdd), [self.n], dtype)[0]
 
     def fd_batch_host(self, q, qd, tau, dtype=np.float64):
         """Blocking host form: multibody_fd_batch_host_f64 (default) or _f32 (dtype=np.float32)."""
-        return self._host_call("fd", (q, qd, tau), dtype)
+        return self._host_call("fd", (q, qd, tau), [self.n], dtype)[0]
 
     def rnea_fd_batch_host(self, q, qd, qdd, tau_in, dtype=np.float64):
         """Blocking host form of rnea_fd_batch: (tau, qdd_out) as [n, B] numpy arrays
         (multibody_rnea_fd_batch_host_f64, or _f32 with dtype=np.float32)."""
-        arrs = _host_soa((q, qd, qdd, tau_in), self.n, dtype)
-        B = arrs[0].shape[1]
-        outs = [np.empty_like(arrs[0]) for _ in range(2)]
-        f32 = arrs[0].dtype == np.float32
-        fn = getattr(_lib, f"multibody_rnea_fd_batch_host_{'f32' if f32 else 'f64'}")
-        ptr = _fp if f32 else _dp
-        _check(fn(self._h, *[a.ctypes.data_as(ptr) for a in arrs + outs], B), "rnea_fd_batch_host")
-        return outs[0], outs[1]
+        return tuple(self._host_call("rnea_fd", (q, qd, qdd, tau_in), [self.n] * 2, dtype))
 
     def rnea_deriv_batch_host(self, q, qd, qdd, dtype=np.float64):
         """Blocking host form of rnea_deriv_batch: (dtau_dq, dtau_dqd) as [n*n, B] numpy arrays."""
-        arrs = _host_soa((q, qd, qdd), self.n, dtype)
-        B = arrs[0].shape[1]
-        outs = [np.empty((self.n * self.n, B), dtype=arrs[0].dtype) for _ in range(2)]
-        fn = getattr(_lib, f"multibody_rnea_deriv_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
-        _check(fn(self._h, *[a.ctypes.data for a in arrs + outs], B), "rnea_deriv_batch_host")
-        return outs[0], outs[1]
+        return tuple(self._host_call("rnea_deriv", (q, qd, qdd), [self.n * self.n] * 2, dtype))
 
     def fd_deriv_batch_host(self, q, qd, tau, dtype=np.float64):
         """Blocking host form of fd_deriv_batch: (qdd [n, B], dqdd_dq, dqdd_dqd, dqdd_dtau [n*n, B])."""
-        arrs = _host_soa((q, qd, tau), self.n, dtype)
-        B = arrs[0].shape[1]
-        outs = [np.empty_like(arrs[0])] + [np.empty((self.n * self.n, B), dtype=arrs[0].dtype) for _ in range(3)]
-        fn = getattr(_lib, f"multibody_fd_deriv_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
-        _check(fn(self._h, *[a.ctypes.data for a in arrs + outs], B), "fd_deriv_batch_host")
-        return tuple(outs)
-
-    def _host_call(self, kind, ins, dtype):
-        arrs = _host_soa(ins, self.n, dtype)
-        B = arrs[0].shape[1]
-        out = np.empty_like(arrs[0])
-        f32 = arrs[0].dtype == np.float32
-        fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if f32 else 'f64'}")
-        ptr = _fp if f32 else _dp
-        _check(fn(self._h, *[a.ctypes.data_as(ptr) for a in arrs], out.ctypes.data_as(ptr), B),
-               f"{kind}_batch_host")
-        return out
+        return tuple(self._host_call("fd_deriv", (q, qd, tau), [self.n] + [self.n * self.n] * 3, dtype))
 
 
 def to_tiled(x, stream=None):

@@ -180,6 +180,36 @@ def test_want_subsets_and_ld(ffi, dev):
     assert torch.equal(out[1][:, :B], dqd) and bool((out[1][:, B:] == -77.0).all())
 
 
+def test_host_forms_skip_null_outputs(ffi, dev):
+    """The blocking host forms with one output NULL (the wrappers never pass one): the device
+    scratch offsets of the later outputs then depend on which are present.  Each result equals the
+    device-pointer form's with the same output NULL bit for bit -- the same kernel, the same launch
+    -- and the skipped output's host buffer is never written.  B = 257: one full block and a tail."""
+    c = _case(ffi, "fr3", "f64")
+    mb, B, n = c["mb"], 257, 7
+    lib = ffi.lib()
+    s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    for name, which, rows, skip in (("fd_deriv", (0, 1, 3), (n, n * n, n * n, n * n), 1),
+                                    ("rnea_deriv", (0, 1, 2), (n * n, n * n), 1)):
+        host_in = [np.ascontiguousarray(c["x"][i][:, :B]) for i in which]
+        dev_in = _dev_inputs(c, dev, "f64", B, which)
+        dev_out = [torch.full((r, B), -77.0, dtype=torch.float64, device=dev) for r in rows]
+        ptrs = [None if k == skip else o.data_ptr() for k, o in enumerate(dev_out)]
+        fn = getattr(lib, f"multibody_{name}_batch_f64")
+        assert fn(mb.handle, *[t.data_ptr() for t in dev_in], *ptrs, B, B, s) == 0, ffi.last_error()
+        torch.cuda.synchronize(dev)
+        host_out = [np.full((r, B), -77.0) for r in rows]
+        hptrs = [None if k == skip else o.ctypes.data for k, o in enumerate(host_out)]
+        fn = getattr(lib, f"multibody_{name}_batch_host_f64")
+        assert fn(mb.handle, *[a.ctypes.data for a in host_in], *hptrs, B) == 0, ffi.last_error()
+        for k, (h, d) in enumerate(zip(host_out, dev_out)):
+            if k == skip:
+                assert np.all(h == -77.0) and bool((d == -77.0).all()), (name, k)  # untouched
+            else:
+                assert np.all(np.isfinite(h)), (name, k)
+                assert np.array_equal(h.view(np.int64), d.cpu().numpy().view(np.int64)), (name, k)  # bit for bit
+
+
 def _fd_identities(c, outs, B):
     """(|H X_tau - I|, |H X_q + dtau_dq|, |H X_qd + dtau_dqd|) scaled, fp64 outputs."""
     Hs, _, rq, rqd = _fd_ref(c)
