@@ -366,6 +366,73 @@ int multibody_rnea_deriv(const Multibody *mb, const double *q, const double *qd,
 int multibody_fd_deriv(const Multibody *mb, const double *q, const double *qd, const double *tau, double *qdd,
                        double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau);
 
+/* ---- reverse-mode gradient of the fused rollout -------------------------------- */
+/* The vector-Jacobian product of K rollout steps (multibody_rollout_batch_*), for gradient-based
+ * shooting.  Step k reads the state (q_k, v_k) and tau_k:
+ *   a_k = fd(q_k, v_k, tau_k)     v_{k+1} = v_k + dt a_k     q_{k+1} = q_k + dt v_{k+1}
+ * Inputs: the initial state q, qd, the torques tau_seq, and cotangents gq[k], gqd[k] of the state
+ * after step k, k = 0 .. K-1 -- gq[k] pairs with traj[k] of the rollout, gqd[k] with the velocity at
+ * the same instant (gqd[K-1] with the final qd).  Outputs: the gradient of
+ *   L = sum_k gq[k] . q_{k+1} + gqd[k] . v_{k+1}
+ * with respect to the initial state (g_q0, g_qd0) and every torque (g_tau), the size of the inputs;
+ * no Jacobian matrix is formed or stored.  One launch: the trajectory is recomputed forward, each
+ * pre-step state parked in `work`, then the adjoint recursion runs backward (one forward-dynamics
+ * factorisation, two solves and the tangent column sweeps of multibody_fd_deriv_batch_* per step,
+ * each column dotted with the adjoint as it completes; rollout_vjp_body.hip.hpp).
+ *
+ * Layout: q, qd, g_q0, g_qd0 are [n][ld]; tau_seq, gq, gqd, g_tau are [K][n][ld] (step k, joint j,
+ * configuration b at (k*n + j)*ld + b, as the rollout's tau_seq); work is [K][2n][ld] of scratch
+ * the caller provides, its contents on return unspecified.  Every array is required.  Checks, in
+ * order: handle, batch >= 0, ld >= batch, batch == 0 (RB_OK, nothing else looked at), K < 0
+ * ("negative step count") or K == 0 (nothing to differentiate) RB_ERR_ARG, a NULL array RB_ERR_NULL,
+ * an output or the workspace that is also an input or passed twice RB_ERR_ARG, then the scope.
+ * Batches are split at 2^28 per launch.
+ *
+ * Scope: as multibody_fd_deriv_batch_* -- serial revolute chains (z-axis or
+ * RB_MODEL_GENERAL_AXES) on the mass-matrix forward dynamics, up to 12 links; anything else returns
+ * RB_ERR_UNSUPPORTED and rb_last_error() names the condition.  A model-specialised (hipRTC) kernel
+ * only: with hipRTC disabled or failed RB_ERR_UNSUPPORTED with the log.  SoA rows only.
+ *
+ * Relation to multibody_rollout_batch_*: the trajectory differentiated is the rollout of the
+ * mass-matrix forward dynamics.  For chains of 9 to 12 links multibody_rollout_batch_* integrates
+ * the articulated-body form instead, so the two trajectories agree to rounding, not bit for bit.
+ *
+ * Input domain: q_k, v_k and tau_k are checked at every step; a configuration that leaves the domain
+ * at any step (a NaN / Inf input, an angle past the bound, also one the integration runs into) gets
+ * NaN in every element of g_q0, g_qd0 and g_tau, the others are unaffected.  The cotangents gq, gqd
+ * are NOT checked: a NaN there propagates by arithmetic into the outputs it reaches.
+ *
+ * Accuracy (tests/test_rollout_vjp_host.py, tests/test_gpu_rollout_vjp.py; reference: Richardson
+ * central differences of the fp64 oracle's own rollout along a random direction): fp64
+ * |<g, d> - ref| <= 1e-7 (1 + |ref|) wherever that reference is self-consistent to 1e-8 (measured
+ * 2e-12 FR3, 2e-11 on 12 links, K = 3); the kernel agrees with the host form of the same lane body to
+ * 1.02e-13 relative (measured 1.02e-14, K = 3).  fp32 against the fp64 kernel on the same
+ * fp32-rounded inputs (B = 257, K = 3, dt = 0.01), per output array and configuration:
+ * max|d| <= 4e-4 (1 + max|ref|) (measured 5.1e-6 FR3, 9.7e-5 on 12 links). */
+int multibody_rollout_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq,
+                                    double dt, int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0,
+                                    float *g_tau, float *work, int64_t batch, int64_t ld, void *stream);
+int multibody_rollout_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                    double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                                    double *g_tau, double *work, int64_t batch, int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch); the workspace is internal. */
+int multibody_rollout_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq,
+                                         double dt, int K, const float *gq, const float *gqd, float *g_q0,
+                                         float *g_qd0, float *g_tau, int64_t batch);
+int multibody_rollout_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                         double dt, int K, const double *gq, const double *gqd, double *g_q0,
+                                         double *g_qd0, double *g_tau, int64_t batch);
+/* One configuration, fp64, [K][n] arrays, on the calling thread: the same lane body compiled for
+ * the host, its workspace internal (an FMA3 / AVX2 CPU, else RB_ERR_UNSUPPORTED). */
+int multibody_rollout_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau_seq, double dt,
+                          int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0, double *g_tau);
+/* Inspection of that kernel (it has no kind number in the multibody_*_ex queries above): the
+ * generated source / the hipRTC compile for `arch` of the kernel a launch of `batch`
+ * configurations runs, as multibody_jit_source_ex / multibody_jit_compile_ex; a model out of scope
+ * has the empty source and -RB_ERR_UNSUPPORTED. */
+int multibody_rollout_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_rollout_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

@@ -275,6 +275,17 @@ hipError_t launch_fd_deriv(const Multibody *mb, const T *q, const T *qd, const T
                       [&] { return no_generic(mb, "the dynamics derivatives run"); });
 }
 
+// The rollout's reverse-mode gradient (rollout_vjp_body.hip.hpp): a model-specialised kernel only,
+// SoA rows, as the derivatives above.
+template <typename T>
+hipError_t launch_rollout_vjp(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, T dt, int K, const T *gq,
+                              const T *gqd, T *g_q0, T *g_qd0, T *g_tau, T *work, uint32_t B, int64_t ld,
+                              hipStream_t s) {
+    void *args[] = {&q, &qd, &tau_seq, &dt, &K, &gq, &gqd, &g_q0, &g_qd0, &g_tau, &work, &B, &ld};
+    return launch_any(mb, rbamd::JitKind::RolloutVjp, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the rollout gradient runs"); });
+}
+
 constexpr int64_t kChunk = int64_t(1) << 28;  // per-launch batch cap: b * sizeof(T) < 2^32
 
 int check_batch(const Multibody *mb, int64_t batch, int64_t ld) {
@@ -543,6 +554,36 @@ int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt,
     });
 }
 
+// The rollout gradient's checks after handle / batch / ld and the empty-batch return: the step
+// count, then (`arrays`) every array present, no output or the workspace aliased, a model in scope.
+int vjp_steps_ok(int K) {
+    if (K < 0) return set_err(RB_ERR_ARG, "negative step count");
+    if (K == 0) return set_err(RB_ERR_ARG, "rollout_vjp: K == 0 steps, nothing to differentiate");
+    return RB_OK;
+}
+
+template <typename T>
+int vjp_args_ok(const Multibody *mb, std::initializer_list<const T *> in, std::initializer_list<const T *> out) {
+    for (const T *p : out)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    return deriv_args_ok<T>(mb, rbamd::JitKind::RolloutVjp, "rollout_vjp", in, out);
+}
+
+template <typename T>
+int rollout_vjp_batch(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
+                      const T *gqd, T *g_q0, T *g_qd0, T *g_tau, T *work, int64_t batch, int64_t ld, void *stream) {
+    auto args_ok = [&] {
+        if (int rc = vjp_steps_ok(K)) return rc;
+        return vjp_args_ok<T>(mb, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau, work});
+    };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "rollout_vjp launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;  // tau_seq, gq, gqd, g_tau: K * n rows; work: 2 K n
+        return launch_rollout_vjp<T>(mb, at(q, n), at(qd, n), at(tau_seq, K * n), (T)dt, K, at(gq, K * n),
+                                     at(gqd, K * n), at(g_q0, n), at(g_qd0, n), at(g_tau, K * n), at(work, 2 * K * n), nb,
+                                     ld, (hipStream_t)stream);
+    });
+}
+
 template <typename T>
 int crba_batch(const Multibody *mb, const T *q, T *H, int64_t batch, int64_t ld, void *stream, bool tiled = false) {
     return batch_call<T>(mb, batch, ld, tiled, [&] { return no_null({q, H}); }, "crba launch",
@@ -580,9 +621,12 @@ namespace {
 // takes no scratch: the device offsets depend on which outputs are present).  check() is the
 // entry point's own argument check, after the handle / batch / NULL checks and before any device
 // work; launch(d_in[], d_out[], stream) gets the device arrays (NULL for a skipped output).
+// host_call_rows: inputs of in_rows[k] rows, and `scratch_rows` more rows of device scratch handed to
+// launch as d_out[NOUT] (a workspace no host array stands behind).
 template <typename T, int NIN, int NOUT, typename Check, typename Launch>
-int host_call(const Multibody *mb, const T *const (&in)[NIN], T *const (&out)[NOUT], const int64_t (&rows)[NOUT],
-              bool null_outputs, int64_t batch, Check check, Launch launch) {
+int host_call_rows(const Multibody *mb, const T *const (&in)[NIN], const int64_t (&in_rows)[NIN], T *const (&out)[NOUT],
+                   const int64_t (&rows)[NOUT], int64_t scratch_rows, bool null_outputs, int64_t batch, Check check,
+                   Launch launch) {
     int rc = check_batch(mb, batch, batch);
     if (rc) return rc;
     if (batch == 0) return RB_OK;
@@ -591,23 +635,29 @@ int host_call(const Multibody *mb, const T *const (&in)[NIN], T *const (&out)[NO
     for (const T *p : out)
         if (!p && !null_outputs) return set_err(RB_ERR_NULL, "NULL array");
     if ((rc = check())) return rc;
-    const size_t per = (size_t)mb->model.n * (size_t)batch;
-    size_t total = per * NIN, at[NOUT];
+    size_t total = 0, in_at[NIN], at[NOUT + 1];
+    for (int k = 0; k < NIN; ++k) {
+        in_at[k] = total;
+        total += (size_t)in_rows[k] * (size_t)batch;
+    }
     for (int k = 0; k < NOUT; ++k) {
         at[k] = total;
         if (out[k]) total += (size_t)rows[k] * (size_t)batch;
     }
+    at[NOUT] = total;
+    total += (size_t)scratch_rows * (size_t)batch;
     T *d = nullptr;
     hipStream_t s = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
     if (e != hipSuccess) return hip_err(e, "hipStreamCreate");
     e = hipMallocAsync((void **)&d, total * sizeof(T), s);
     if (e != hipSuccess) { (void)hipStreamDestroy(s); return hip_err(e, "hipMallocAsync"); }
-    T *din[NIN], *dout[NOUT];
-    for (int k = 0; k < NIN; ++k) din[k] = d + k * per;
+    T *din[NIN], *dout[NOUT + 1];
+    for (int k = 0; k < NIN; ++k) din[k] = d + in_at[k];
     for (int k = 0; k < NOUT; ++k) dout[k] = out[k] ? d + at[k] : nullptr;
+    dout[NOUT] = scratch_rows ? d + at[NOUT] : nullptr;
     for (int k = 0; k < NIN && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(din[k], in[k], per * sizeof(T), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(din[k], in[k], (size_t)in_rows[k] * (size_t)batch * sizeof(T), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) rc = launch(din, dout, s);
     else rc = hip_err(e, "hipMemcpyAsync H2D");
     for (int k = 0; k < NOUT && rc == RB_OK; ++k) {
@@ -620,6 +670,14 @@ int host_call(const Multibody *mb, const T *const (&in)[NIN], T *const (&out)[NO
     if (rc == RB_OK && e != hipSuccess) rc = hip_err(e, "hipStreamSynchronize");
     (void)hipStreamDestroy(s);
     return rc;
+}
+
+template <typename T, int NIN, int NOUT, typename Check, typename Launch>
+int host_call(const Multibody *mb, const T *const (&in)[NIN], T *const (&out)[NOUT], const int64_t (&rows)[NOUT],
+              bool null_outputs, int64_t batch, Check check, Launch launch) {
+    int64_t in_rows[NIN];
+    for (int64_t &r : in_rows) r = mb ? mb->model.n : 0;
+    return host_call_rows<T, NIN, NOUT>(mb, in, in_rows, out, rows, 0, null_outputs, batch, check, launch);
 }
 
 const auto no_check = [] { return (int)RB_OK; };
@@ -668,6 +726,23 @@ int fd_deriv_host(const Multibody *mb, const T *q, const T *qd, const T *tau, T 
         [&] { return deriv_args_ok<T>(mb, rbamd::JitKind::FdDeriv, "fd_deriv", {q, qd, tau}, {qdd, dq, dqd, dtau}); },
         [&](T **i, T **o, hipStream_t s) {
             return fd_deriv_batch<T>(mb, i[0], i[1], i[2], o[0], o[1], o[2], o[3], batch, batch, s);
+        });
+}
+
+template <typename T>
+int rollout_vjp_host(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
+                     const T *gqd, T *g_q0, T *g_qd0, T *g_tau, int64_t batch) {
+    // the step count comes before the arrays, as in the device form
+    int rc = check_batch(mb, batch, batch);
+    if (rc) return rc;
+    if (batch == 0) return RB_OK;
+    if ((rc = vjp_steps_ok(K))) return rc;
+    const int64_t n = mb->model.n, kn = (int64_t)K * n;
+    return host_call_rows<T, 5, 3>(
+        mb, {q, qd, tau_seq, gq, gqd}, {n, n, kn, kn, kn}, {g_q0, g_qd0, g_tau}, {n, n, kn}, 2 * kn, false, batch,
+        [&] { return vjp_args_ok<T>(mb, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau}); },
+        [&](T **i, T **o, hipStream_t s) {
+            return rollout_vjp_batch<T>(mb, i[0], i[1], i[2], dt, K, i[3], i[4], o[0], o[1], o[2], o[3], batch, batch, s);
         });
 }
 }  // namespace
@@ -838,7 +913,7 @@ uint32_t launch_size(int64_t batch) { return batch < kChunk ? (uint32_t)batch : 
 
 int check_kernel_query(const Multibody *mb, int kind, int64_t batch) {
     if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
-    if (kind < 0 || kind >= rbamd::kJitKinds) return set_err(RB_ERR_ARG, kKindMsg);
+    if (kind < 0 || kind >= rbamd::kJitPublicKinds) return set_err(RB_ERR_ARG, kKindMsg);
     if (batch < 1) return set_err(RB_ERR_ARG, "batch must be positive");
     // a kind that has no kernel for this model (the derivative kinds outside their scope)
     return deriv_supported(mb, (rbamd::JitKind)kind);
@@ -863,6 +938,35 @@ std::string shaped_source(const Multibody *mb, int kind, bool f64, int64_t batch
     t_key = key;
     t_src = src;
     return src;
+}
+
+// The rollout gradient's kernel has no public kind number: its two inspection entry points check
+// the handle, the batch and the model's scope here.
+int check_vjp_query(const Multibody *mb, int64_t batch) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (batch < 1) return set_err(RB_ERR_ARG, "batch must be positive");
+    return deriv_supported(mb, rbamd::JitKind::RolloutVjp);
+}
+
+// rc: the query's check; a kind with no kernel for this model (RB_ERR_UNSUPPORTED) has the empty source.
+int source_query(const Multibody *mb, int rc, int kind, int f64, int64_t batch, int tiled, char *buf, int64_t cap) {
+    if (rc && rc != RB_ERR_UNSUPPORTED) return -rc;
+    const std::string src = rc ? std::string() : shaped_source(mb, kind, f64 != 0, batch, tiled != 0);
+    if (buf && cap > 0) {
+        const size_t n = src.size() < (size_t)(cap - 1) ? src.size() : (size_t)(cap - 1);
+        std::memcpy(buf, src.data(), n);
+        buf[n] = 0;
+    }
+    return (int)src.size();
+}
+
+int64_t compile_query(const Multibody *mb, int kind, int f64, int64_t batch, int tiled, const char *arch) {
+    const rbamd::JitVariant v =
+        rbamd::jit_resolve(mb->model, (rbamd::JitKind)kind, f64 != 0, launch_size(batch), tiled != 0, fast_trig());
+    std::vector<char> code;
+    std::string err;
+    if (!rbamd::jit_compile(mb->model, v, arch ? arch : "gfx950", &code, &err)) return -set_err(RB_ERR_HIP, err);
+    return (int64_t)code.size();
 }
 
 void note_jit_errors(const Multibody *mb) {
@@ -901,16 +1005,11 @@ int multibody_jit_source(const Multibody *mb, int kind, int f64, char *buf, int6
 }
 
 int multibody_jit_source_ex(const Multibody *mb, int kind, int f64, int64_t batch, int tiled, char *buf, int64_t cap) {
-    int rc = check_kernel_query(mb, kind, batch);
-    if (rc && rc != RB_ERR_UNSUPPORTED) return -rc;
-    // a kind with no kernel for this model: the empty source
-    const std::string src = rc ? std::string() : shaped_source(mb, kind, f64 != 0, batch, tiled != 0);
-    if (buf && cap > 0) {
-        const size_t n = src.size() < (size_t)(cap - 1) ? src.size() : (size_t)(cap - 1);
-        std::memcpy(buf, src.data(), n);
-        buf[n] = 0;
-    }
-    return (int)src.size();
+    return source_query(mb, check_kernel_query(mb, kind, batch), kind, f64, batch, tiled, buf, cap);
+}
+
+int multibody_rollout_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_vjp_query(mb, batch), (int)rbamd::JitKind::RolloutVjp, f64, batch, 0, buf, cap);
 }
 
 int64_t multibody_jit_compile(const Multibody *mb, int kind, int f64, const char *arch) {
@@ -919,12 +1018,12 @@ int64_t multibody_jit_compile(const Multibody *mb, int kind, int f64, const char
 
 int64_t multibody_jit_compile_ex(const Multibody *mb, int kind, int f64, int64_t batch, int tiled, const char *arch) {
     if (int rc = check_kernel_query(mb, kind, batch)) return -rc;
-    const rbamd::JitVariant v =
-        rbamd::jit_resolve(mb->model, (rbamd::JitKind)kind, f64 != 0, launch_size(batch), tiled != 0, fast_trig());
-    std::vector<char> code;
-    std::string err;
-    if (!rbamd::jit_compile(mb->model, v, arch ? arch : "gfx950", &code, &err)) return -set_err(RB_ERR_HIP, err);
-    return (int64_t)code.size();
+    return compile_query(mb, kind, f64, batch, tiled, arch);
+}
+
+int64_t multibody_rollout_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_vjp_query(mb, batch)) return -rc;
+    return compile_query(mb, (int)rbamd::JitKind::RolloutVjp, f64, batch, 0, arch);
 }
 
 int multibody_upload(const Multibody *mb) {
@@ -1123,6 +1222,39 @@ int multibody_fd_deriv_batch_host_f64(const Multibody *mb, const double *q, cons
                                       double *qdd_out, double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau,
                                       int64_t batch) {
     return fd_deriv_host<double>(mb, q, qd, tau, qdd_out, dqdd_dq, dqdd_dqd, dqdd_dtau, batch);
+}
+
+// ------------------------------------------------------------- gradient of the rollout
+int multibody_rollout_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq, double dt,
+                                    int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0, float *g_tau,
+                                    float *work, int64_t batch, int64_t ld, void *stream) {
+    return rollout_vjp_batch<float>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
+}
+int multibody_rollout_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                    double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                                    double *g_tau, double *work, int64_t batch, int64_t ld, void *stream) {
+    return rollout_vjp_batch<double>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
+}
+int multibody_rollout_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq,
+                                         double dt, int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0,
+                                         float *g_tau, int64_t batch) {
+    return rollout_vjp_host<float>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
+}
+int multibody_rollout_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                         double dt, int K, const double *gq, const double *gqd, double *g_q0,
+                                         double *g_qd0, double *g_tau, int64_t batch) {
+    return rollout_vjp_host<double>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
+}
+
+int multibody_rollout_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau_seq, double dt, int K,
+                          const double *gq, const double *gqd, double *g_q0, double *g_qd0, double *g_tau) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = vjp_steps_ok(K)) return rc;
+    if (int rc = vjp_args_ok<double>(mb, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau})) return rc;
+    if (!rbamd::host_rollout_vjp(mb->model, mb->pk64.data(), q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau))
+        return set_err(RB_ERR_UNSUPPORTED, "rollout_vjp: the single-configuration form runs on the host and needs an "
+                                           "FMA3 / AVX2 CPU");
+    return RB_OK;
 }
 
 // Single configuration, fp64, on the calling thread: the lane body compiled for the host

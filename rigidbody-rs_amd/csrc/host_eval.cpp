@@ -13,7 +13,9 @@
 // (the recursion is written in fused multiply-adds); without it the GPU path serves.
 #include "host_eval.hpp"
 
-#include "rnea_deriv_body.hip.hpp"  // first: it declares the host reciprocal fdh_body's L D L^T takes
+#include <vector>
+
+#include "rollout_vjp_body.hip.hpp"  // first: rnea_deriv_body declares the host reciprocal fdh_body's L D L^T takes
 #include "crba_body.hip.hpp"
 #include "dofs.hpp"
 #include "kernels.hpp"
@@ -161,6 +163,51 @@ RB_HOST_FMA bool fd_deriv_fma(int n, const double *mdl, const double *q, const d
     }
 }
 
+template <int N>
+RB_HOST_FMA bool rollout_vjp_fma_n(const double *mdl, const double *q, const double *qd, const double *tau_seq,
+                                   double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                                   double *g_tau, double *work) {
+    if constexpr (N <= kHostFdDerivMaxLinks) {
+        double a[N], b[N];
+        for (int j = 0; j < N; ++j) {
+            a[j] = q[j];
+            b[j] = qd[j];
+        }
+        dev::rollout_vjp_eval<double, N, false>(
+            mdl, a, b, dt, K,
+            [&](int k, double(&tv)[N]) {
+                for (int j = 0; j < N; ++j) tv[j] = tau_seq[(size_t)k * N + j];
+            },
+            [&](int k, double(&x)[N], double(&y)[N]) {
+                for (int j = 0; j < N; ++j) {
+                    x[j] = gq[(size_t)k * N + j];
+                    y[j] = gqd[(size_t)k * N + j];
+                }
+            },
+            [&](int k, int r, double v) { work[(size_t)k * 2 * N + r] = v; }, [&](int k, int r) { return work[(size_t)k * 2 * N + r]; },
+            [&](int k, int j, double v) { g_tau[(size_t)k * N + j] = v; },
+            [&](int j, double x, double y) {
+                g_q0[j] = x;
+                g_qd0[j] = y;
+            });
+        return true;
+    } else {
+        return false;
+    }
+}
+
+RB_HOST_FMA bool rollout_vjp_fma(int n, const double *mdl, const double *q, const double *qd, const double *tau_seq,
+                                 double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                                 double *g_tau, double *work) {
+    switch (n) {
+#define X(N) \
+    case N: return rollout_vjp_fma_n<N>(mdl, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work);
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -195,6 +242,14 @@ bool host_fd_deriv(const Model &m, const double *pk, const double *q, const doub
                    double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau) {
     return host_eval_supported(m) && m.n <= kHostFdDerivMaxLinks &&
            fd_deriv_fma(m.n, pk, q, qd, tau, qdd, dqdd_dq, dqdd_dqd, dqdd_dtau);
+}
+
+bool host_rollout_vjp(const Model &m, const double *pk, const double *q, const double *qd, const double *tau_seq,
+                      double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                      double *g_tau) {
+    if (!host_eval_supported(m) || m.n > kHostFdDerivMaxLinks || K < 1) return false;
+    std::vector<double> work((size_t)K * 2 * m.n);
+    return rollout_vjp_fma(m.n, pk, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work.data());
 }
 
 }  // namespace rbamd

@@ -28,4 +28,10 @@ bool host_fd_deriv(const Model &m, const double *pk, const double *q, const doub
                    double *dqdd_dq, double *dqdd_dqd, double *dqdd_dtau);
 constexpr int kHostFdDerivMaxLinks = 12;
 
+// Reverse-mode gradient of the K-step rollout (rollout_vjp_body.hip.hpp), host_fd_deriv's scope:
+// tau_seq, gq, gqd, g_tau [K][n], the rest [n]; the workspace is internal.  K >= 1.
+bool host_rollout_vjp(const Model &m, const double *pk, const double *q, const double *qd, const double *tau_seq,
+                      double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                      double *g_tau);
+
 }  // namespace rbamd

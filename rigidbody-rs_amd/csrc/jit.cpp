@@ -142,12 +142,12 @@ int fd_form(const ModelShape &m, JitKind kind) {
 int jit_fd_form(const Model &m, JitKind kind) { return fd_form({m.n, m.serial_revolute()}, kind); }
 
 std::string jit_kind_unsupported(const Model &m, JitKind kind) {
-    if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv) return "";
-    const char *name = kind == JitKind::RneaDeriv ? "rnea_deriv" : "fd_deriv";
+    if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv && kind != JitKind::RolloutVjp) return "";
+    const char *name = kind == JitKind::RneaDeriv ? "rnea_deriv" : kind == JitKind::FdDeriv ? "fd_deriv" : "rollout_vjp";
     if (!m.serial_revolute())
         return std::string(name) + ": no such kernel for this model: serial revolute chains only (kinematic trees, "
                "prismatic joints and a floating base are not supported)";
-    if (kind == JitKind::FdDeriv && jit_fd_form(m, JitKind::Fd) != 2)
+    if (kind != JitKind::RneaDeriv && jit_fd_form(m, JitKind::Fd) != 2)
         return std::string(name) + ": no such kernel for this model: it needs the mass-matrix forward dynamics "
                "(serial chains up to 12 links, fd_form 2); this model has " + std::to_string(m.n) +
                " links on the articulated-body form";
@@ -310,12 +310,19 @@ static bool jit_no_licm(const Model &m, const JitVariant &v) {
     return v.kind == JitKind::Rollout && jit_rollout_no_hoist(v.f64, m.n, v.pack);
 }
 
+// The rollout's gradient is built without the SLP vectorizer: it pairs the fp32 column sweeps'
+// independent FMAs into 2-wide operations whose register pairs cost more than the packed
+// arithmetic saves (FR3 fp32: 512 registers and 840 B of scratch per lane with it, 194 and none
+// without; fp64 380 / 386, no scratch either way).
+static bool jit_no_slp(const JitVariant &v) { return v.kind == JitKind::RolloutVjp; }
+
 std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const JitKind kind = v.kind;
     const bool f64 = v.f64;
     const int pack = v.pack;
     const bool deriv = kind == JitKind::RneaDeriv || kind == JitKind::FdDeriv;
-    if (deriv && !jit_kind_unsupported(m, kind).empty()) return "";
+    const bool vjp = kind == JitKind::RolloutVjp;  // the rollout's adjoint: fd_deriv's scope and link forces
+    if ((deriv || vjp) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
         double *c = &pk[(size_t)i * kLinkStride];
@@ -357,7 +364,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     // 131 instead of 125 VGPRs (3 waves/SIMD instead of 4), and all its grid forms (pairs,
     // single tail, one per lane below 2^19) must stay bit-identical to each other.
     const bool dyn = kind == JitKind::Rnea || kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd ||
-                     deriv;
+                     deriv || vjp;
     // jit_variant bit 16384 (A/B): the centre-of-mass form for the fp64 RNEA too
     // rnea_lane_rev: the fp64 RNEA of serial chains longer than 8 links, whose per-link forces
     // hold one wave per SIMD (12 links 264 VGPRs, 30 links 496) and do not fit LDS either
@@ -435,7 +442,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         }
         o << "};\n";
     }
-    o << (deriv                                             ? "#include \"rnea_deriv_body.hip.hpp\"\n"
+    o << (vjp                                               ? "#include \"rollout_vjp_body.hip.hpp\"\n"
+          : deriv                                           ? "#include \"rnea_deriv_body.hip.hpp\"\n"
           : kind == JitKind::Rnea                             ? "#include \"rnea_body.hip.hpp\"\n"
           : fdh                                               ? "#include \"fdh_body.hip.hpp\"\n"
           : (kind == JitKind::Fd || kind == JitKind::Rollout) ? "#include \"aba_body.hip.hpp\"\n"
@@ -592,6 +600,14 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         else
             o << "  rbamd::dev::rnea_deriv_lane<T, N, " << F
               << ">(kModel, q + o, qd + o, qdd + o, dq ? dq + o : nullptr, dqd ? dqd + o : nullptr, threadIdx.x, ld);\n}\n";
+    } else if (vjp) {
+        // one configuration per lane on SoA rows, K steps forward then K back (rollout_vjp_body.hip.hpp)
+        sig("const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ tau_seq, T dt, int K, "
+            "const T *__restrict__ gq, const T *__restrict__ gqd, T *__restrict__ g_q0, T *__restrict__ g_qd0, "
+            "T *__restrict__ g_tau, T *work, uint32_t B, int64_t ld");
+        o << lane_guard;
+        o << "  rbamd::dev::rollout_vjp_lane<T, N, " << F
+          << ">(kModel, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, b, ld);\n}\n";
     } else if (kind == JitKind::Rollout) {
         sig(rollout_params);
         if (pack == 4) {
@@ -639,7 +655,7 @@ unsigned jit_grid(const JitKernel &jk, uint32_t B) {
 }
 
 namespace {
-bool rtc_compile(const std::string &src, const std::string &arch, bool no_licm, std::vector<char> *code,
+bool rtc_compile(const std::string &src, const std::string &arch, bool no_licm, bool no_slp, std::vector<char> *code,
                  std::string *error) {
     hiprtcProgram prog = nullptr;
     if (hiprtcCreateProgram(&prog, src.c_str(), "rb_jit.hip", kJitHeaderCount, kJitHeaderSources,
@@ -654,6 +670,7 @@ bool rtc_compile(const std::string &src, const std::string &arch, bool no_licm, 
         optv.push_back("-mllvm");
         optv.push_back("-disable-machine-licm");
     }
+    if (no_slp) optv.push_back("-fno-slp-vectorize");
     const int preload = tuning().kernarg_preload;
     const std::string preload_opt = "-amdgpu-kernarg-preload-count=" + std::to_string(preload);
     if (preload > 0) {
@@ -688,7 +705,8 @@ bool jit_compile(const Model &m, const JitVariant &v, const std::string &arch, s
     }
     std::string src = jit_source(m, v, -1);
     const bool no_licm = jit_no_licm(m, v);
-    if (!rtc_compile(src, arch, no_licm, code, error)) return false;
+    const bool no_slp = jit_no_slp(v);
+    if (!rtc_compile(src, arch, no_licm, no_slp, code, error)) return false;
     // Occupancy cliff (jit.hpp): no target asked for, none in the source, and the kernel just
     // past 256 registers -> rebuild with a 2-wave target; the first build stands if that fails.
     if (tuning().jit_waves < 0 && src.find("amdgpu_waves_per_eu") == std::string::npos) {
@@ -696,7 +714,7 @@ bool jit_compile(const Model &m, const JitVariant &v, const std::string &arch, s
         if (vgprs > 256 && vgprs <= 272) {
             std::string src2 = jit_source(m, v, 2), err2;
             std::vector<char> code2;
-            if (rtc_compile(src2, arch, no_licm, &code2, &err2)) {
+            if (rtc_compile(src2, arch, no_licm, no_slp, &code2, &err2)) {
                 code->swap(code2);
                 src.swap(src2);
             }

@@ -30,13 +30,18 @@ namespace rbamd {
 // RneaDeriv / FdDeriv: analytical derivatives of the inverse / forward dynamics
 // (rnea_deriv_body.hip.hpp), serial revolute chains only -- FdDeriv on the mass-matrix forward
 // dynamics only (jit_kind_unsupported); they have no precompiled generic kernel.
+// RolloutVjp: the reverse-mode gradient of the fused rollout (rollout_vjp_body.hip.hpp), FdDeriv's
+// scope, hipRTC only.  Internal: the public kind numbers of the *_ex inspection queries end at 8
+// (kJitPublicKinds); this kernel is inspected through multibody_rollout_vjp_jit_source / _compile.
 enum class JitKind : int {
-    Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8
+    Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
+    RolloutVjp = 9
 };
-constexpr int kJitKinds = 9;
+constexpr int kJitKinds = 10;
+constexpr int kJitPublicKinds = 9;
 
-// Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds are
-// restricted here; jit_source returns an empty source for a model this refuses.
+// Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds and the
+// rollout's gradient are restricted here; jit_source returns an empty source for a model this refuses.
 std::string jit_kind_unsupported(const Model &m, JitKind kind);
 
 // One compiled kernel of a model: with the model and the tuning knobs (jit_key), everything its

@@ -1,0 +1,51 @@
+"""torch.autograd support for the fused rollout: `rollout(mb, q0, qd0, tau_seq, dt)` is
+Multibody.rollout_batch as a differentiable function of (q0, qd0, tau_seq), its backward one
+Multibody.rollout_vjp_batch launch (rigidbody_batch.h "reverse-mode gradient of the fused rollout").
+
+    traj, qd_final = rollout(mb, q0, qd0, tau_seq, dt)      # [K, n, B], [n, B]
+    cost = ((traj - target) ** 2).sum() + (qd_final ** 2).sum()
+    cost.backward()                                          # q0.grad, qd0.grad, tau_seq.grad
+
+traj[k] is q after step k.  The velocity after an intermediate step is not returned, but the
+integrator is semi-implicit Euler, q_{k+1} = q_k + dt qd_{k+1}, so it is a difference of returned
+positions and a cost on it is written in torch:
+
+    qd_k1 = (traj[k + 1] - traj[k]) / dt                     # qd after step k + 1
+    qd_1 = (traj[0] - q0) / dt                               # ... after the first step
+
+Scope: the gradient's (serial revolute chains on the mass-matrix forward dynamics, up to 12 links).
+For chains of 9 to 12 links the forward rollout integrates the articulated-body form and the
+gradient differentiates the mass-matrix form: the same function to rounding.
+"""
+import torch
+
+
+class _Rollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mb, q0, qd0, tau_seq, dt):
+        q, qd = q0.detach().clone(), qd0.detach().clone()
+        tau = tau_seq.detach().contiguous()
+        traj = mb.rollout_batch(q, qd, tau, dt, traj=True)
+        ctx.mb, ctx.dt = mb, dt
+        ctx.save_for_backward(q0.detach(), qd0.detach(), tau)
+        return traj, qd
+
+    @staticmethod
+    def backward(ctx, grad_traj, grad_qd_final):
+        q0, qd0, tau = ctx.saved_tensors
+        gq = torch.zeros_like(tau) if grad_traj is None else grad_traj.contiguous()
+        gqd = torch.zeros_like(tau)
+        if grad_qd_final is not None:
+            gqd[-1] = grad_qd_final
+        g_q0, g_qd0, g_tau = ctx.mb.rollout_vjp_batch(q0.contiguous(), qd0.contiguous(), tau, ctx.dt, gq, gqd)
+        return None, g_q0, g_qd0, g_tau, None
+
+
+def rollout(mb, q0, qd0, tau_seq, dt):
+    """K semi-implicit Euler steps of the forward dynamics from (q0, qd0) [n, B] under tau_seq
+    [K, n, B] (CUDA tensors, fp32 or fp64; the inputs are not modified): returns (traj [K, n, B],
+    the positions after every step, and qd_final [n, B]), differentiable with respect to q0, qd0 and
+    tau_seq."""
+    if tau_seq.shape[0] < 1:
+        raise ValueError("rollout needs at least one step (tau_seq [K, n, B], K >= 1)")
+    return _Rollout.apply(mb, q0, qd0, tau_seq, float(dt))

@@ -91,6 +91,10 @@ _SIGNATURES = {
     # one configuration, fp64, on the calling thread
     "multibody_rnea_deriv": (_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
     "multibody_fd_deriv": (_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "multibody_rollout_vjp": (_int, [_vp, _dp, _dp, _dp, _dbl, _int] + [_dp] * 5),
+    # inspection of the rollout gradient's kernel: (handle, f64, batch, ...)
+    "multibody_rollout_vjp_jit_source": (_int, [_vp, _int, _i64, _str, _i64]),
+    "multibody_rollout_vjp_jit_compile": (_i64, [_vp, _int, _i64, _str]),
 }
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
 _ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7}
@@ -102,6 +106,9 @@ for _t in ("f32", "f64"):
         if _k not in ("crba", "fwd_kin", "jac"):
             _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
     _SIGNATURES[f"multibody_rollout_batch_{_t}"] = (_int, [_vp, _vp, _vp, _vp, _dbl, _int, _vp, _i64, _i64, _vp])
+    # (handle, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau[, work], batch[, ld, stream])
+    _SIGNATURES[f"multibody_rollout_vjp_batch_{_t}"] = (_int, [_vp] * 4 + [_dbl, _int] + [_vp] * 6 + [_i64, _i64, _vp])
+    _SIGNATURES[f"multibody_rollout_vjp_batch_host_{_t}"] = (_int, [_vp] * 4 + [_dbl, _int] + [_vp] * 5 + [_i64])
     _SIGNATURES[f"rb_fill_uniform_{_t}"] = (_int, [_vp, _int, _i64, _i64, _dp, _dp, _u64, _vp])
     _SIGNATURES[f"rb_to_tiled_{_t}"] = (_int, [_vp, _i64, _vp, _int, _i64, _vp])
     _SIGNATURES[f"rb_from_tiled_{_t}"] = (_int, [_vp, _vp, _i64, _int, _i64, _vp])
@@ -390,6 +397,37 @@ class Multibody:
         _check(_lib.multibody_fd_deriv(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau, qdd, *outs)]), "fd_deriv")
         return (qdd, *(o.reshape(self.n, self.n).T.copy() for o in outs))
 
+    def rollout_vjp(self, q, qd, tau_seq, dt, gq, gqd):
+        """multibody_rollout_vjp: (g_q0 [n], g_qd0 [n], g_tau [K, n]), the gradient of
+        sum_k gq[k] . q_{k+1} + gqd[k] . qd_{k+1} over the K-step rollout from (q, qd) under tau_seq
+        [K, n]; gq, gqd [K, n].  One configuration, on the calling thread."""
+        q, qd = (_dvec(x, self.n) for x in (q, qd))
+        tau_seq, gq, gqd = (np.ascontiguousarray(x, dtype=np.float64) for x in (tau_seq, gq, gqd))
+        K = tau_seq.shape[0] if tau_seq.ndim == 2 else -1
+        for a in (tau_seq, gq, gqd):
+            if a.shape != (K, self.n):
+                raise ValueError(f"tau_seq, gq and gqd must all be [K, {self.n}], got {a.shape}")
+        outs = [np.empty(self.n), np.empty(self.n), np.empty((K, self.n))]
+        _check(_lib.multibody_rollout_vjp(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau_seq)], float(dt), K,
+                                          *[a.ctypes.data_as(_dp) for a in (gq, gqd, *outs)]), "rollout_vjp")
+        return tuple(outs)
+
+    def rollout_vjp_jit_source(self, f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the rollout gradient's kernel (multibody_rollout_vjp_jit_source); the
+        empty string for a model outside its scope."""
+        n = _lib.multibody_rollout_vjp_jit_source(self._h, int(bool(f64)), int(batch), None, 0)
+        if n < 0:
+            raise RigidBodyError(last_error())
+        buf = ctypes.create_string_buffer(n + 1)
+        _lib.multibody_rollout_vjp_jit_source(self._h, int(bool(f64)), int(batch), buf, n + 1)
+        return buf.value.decode()
+
+    def rollout_vjp_jit_compile(self, f64=False, arch="gfx950", batch=1 << 20) -> int:
+        r = _lib.multibody_rollout_vjp_jit_compile(self._h, int(bool(f64)), int(batch), arch.encode())
+        if r < 0:
+            raise RigidBodyError(last_error())
+        return r
+
     # ------------------------------------------------------- batched, device [n, B]
     def _soa_call(self, kind, ins, outs, stream):
         """multibody_<kind>_batch_f32 / _f64 on [rows, B] CUDA tensors.  ins: (tensor, name) pairs,
@@ -531,7 +569,55 @@ class Multibody:
                    "rollout_batch")
         return tr
 
+    def rollout_vjp_batch(self, q, qd, tau_seq, dt, gq, gqd, stream=None):
+        """multibody_rollout_vjp_batch_*: the reverse-mode gradient of rollout_batch in one launch.
+        q, qd [n, B] (the initial state, not modified), tau_seq [K, n, B]; gq, gqd [K, n, B] are the
+        cotangents of the state after step k (gq[k] pairs with traj[k], gqd[K-1] with the final qd).
+        Returns (g_q0 [n, B], g_qd0 [n, B], g_tau [K, n, B]).  The [K, 2n, B] workspace is allocated
+        here.  Every array is contiguous (ld == B), like the rollout's."""
+        q = _soa(q, self.n, "q")
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        qd = _soa(qd, self.n, "qd", q.dtype, B)
+        ld = _same_ld((q, qd))
+        if B > 1 and ld != B:
+            raise ValueError("rollout_vjp needs contiguous [n, B] state (ld == B), like tau_seq")
+        if not isinstance(tau_seq, torch.Tensor) or tau_seq.dim() != 3 or tau_seq.shape[1:] != (self.n, B):
+            raise ValueError(f"tau_seq must be [K, {self.n}, {B}]")
+        K = tau_seq.shape[0]
+        for t, name in ((tau_seq, "tau_seq"), (gq, "gq"), (gqd, "gqd")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (K, self.n, B):
+                raise ValueError(f"{name} must be [{K}, {self.n}, {B}]")
+            if t.dtype != q.dtype or not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous with the state's dtype")
+        dev = _one_device((q, qd, tau_seq, gq, gqd))
+        g_q0, g_qd0, g_tau = torch.empty_like(q), torch.empty_like(qd), torch.empty_like(tau_seq)
+        work = torch.empty((K, 2 * self.n, B), dtype=q.dtype, device=dev)
+        fn = getattr(_lib, f"multibody_rollout_vjp_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau_seq.data_ptr(), float(dt), int(K), gq.data_ptr(),
+                      gqd.data_ptr(), g_q0.data_ptr(), g_qd0.data_ptr(), g_tau.data_ptr(), work.data_ptr(), B,
+                      max(ld, B, 1), _stream_ptr(stream, dev)), "rollout_vjp_batch")
+        return g_q0, g_qd0, g_tau
+
     # -------------------------------------------------------- batched, host [n, B]
+    def rollout_vjp_batch_host(self, q, qd, tau_seq, dt, gq, gqd, dtype=np.float64):
+        """Blocking host form of rollout_vjp_batch on numpy arrays: q, qd [n, B]; tau_seq, gq, gqd
+        [K, n, B].  Returns (g_q0, g_qd0 [n, B], g_tau [K, n, B])."""
+        q, qd = _host_soa((q, qd), self.n, dtype)
+        B = q.shape[1]
+        seqs = [np.ascontiguousarray(x, dtype=q.dtype) for x in (tau_seq, gq, gqd)]
+        K = seqs[0].shape[0] if seqs[0].ndim == 3 else -1
+        for a in seqs:
+            if a.shape != (K, self.n, B):
+                raise ValueError(f"tau_seq, gq and gqd must all be [K, {self.n}, {B}], got {a.shape}")
+        outs = [np.empty_like(q), np.empty_like(q), np.empty_like(seqs[0])]
+        fn = getattr(_lib, f"multibody_rollout_vjp_batch_host_{'f32' if q.dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, q.ctypes.data, qd.ctypes.data, seqs[0].ctypes.data, float(dt), K,
+                  *[a.ctypes.data for a in (seqs[1], seqs[2], *outs)], B), "rollout_vjp_batch_host")
+        return tuple(outs)
+
     def _host_call(self, kind, ins, out_rows, dtype):
         """multibody_<kind>_batch_host_f64 / _f32 (blocking): `ins` as [n, B] numpy arrays of
         `dtype`; returns one new [rows, B] array per entry of out_rows."""
