@@ -433,6 +433,83 @@ int multibody_rollout_vjp(const Multibody *mb, const double *q, const double *qd
 int multibody_rollout_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_rollout_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch);
 
+/* ---- external link wrenches ----------------------------------------------------- */
+/* Inverse and forward dynamics with one external spatial wrench per moving link and configuration
+ * (contact forces, payloads, end-effector loads, thrusters):
+ *   tau = rnea_ext(q, qd, qdd, fext) = rnea(q, qd, qdd) - sum_j J_j(q)^T fext_j
+ *   qdd = fd_ext(q, qd, tau, fext)   = fd(q, qd, tau + sum_j J_j(q)^T fext_j)
+ * J_j is the body Jacobian of link j and fext_j the wrench acting ON link j.
+ *
+ * Frame: fext_j is expressed in link j's own URDF link frame -- the joint's child frame, after the
+ * joint's motion, the frame multibody_fwd_kin / multibody_jac report for the last link -- and
+ * applied at that frame's origin.  With RB_MODEL_GENERAL_AXES (and the tree reading) the kernels
+ * rotate it into their own per-link frame; a caller never sees that frame.
+ *
+ * Layout: fext is [6 n][ld]; component c of link j for configuration b at fext[(6 j + c) * ld + b],
+ * c = 0..2 the force, c = 3..5 the moment -- the [lin; rot] row order of the Jacobian.  So for a
+ * wrench f on the last link only, rnea - rnea_ext = J^T f with J what multibody_jac_batch_* returns.
+ * The six virtual links of a floating base have rows like any other link.  q, qd, qdd, tau are
+ * [n][ld].  fext is required: a caller without forces uses multibody_rnea_batch_* / _fd_batch_*.
+ * The single-configuration forms take fext as [6 n].
+ *
+ * Algorithm (ext_body.hip.hpp; Featherstone 2008): the wrench enters where each link's force is
+ * formed, f_j = I_j a_j + v_j x* I_j v_j - fext_j (Table 5.1) and pA_j = v_j x* I_j v_j - fext_j
+ * (Table 7.1), from rows loaded at link j's forward step.  fd_ext takes the formulation
+ * multibody_fd_batch_* takes for the model: the mass-matrix form for serial chains up to 12 links,
+ * with the bias C = rnea_ext(q, qd, 0, fext), else the articulated-body algorithm.
+ *
+ * Scope: every model the model-specialised kernels run -- serial chains under the reference's
+ * reading or with general axes, of every supported length; kinematic trees; prismatic joints; a
+ * floating base.  Model-specialised (hipRTC) kernels only, no kind number: with hipRTC disabled or
+ * failed RB_ERR_UNSUPPORTED with the log.  SoA rows only (no tiled form), one configuration per
+ * lane, batches split at 2^28 per launch.
+ *
+ * Checks, in order: handle (RB_ERR_NULL), batch >= 0, ld >= batch (RB_ERR_ARG), batch == 0 (RB_OK,
+ * nothing else looked at), a NULL array (RB_ERR_NULL), the output passed as one of the inputs
+ * (RB_ERR_ARG; the device-pointer and single-configuration forms), then hipRTC.
+ *
+ * Input domain: as above, every fext component a value like qd: a configuration with a NaN / Inf in
+ * any input or an angle past the bound gets NaN in every output, the others are unaffected.
+ *
+ * Accuracy (tests/test_ext_host.py, tests/test_gpu_ext.py; reference: the fp64 oracle's rnea / fd
+ * with J^T f composed link by link from its own transforms).  fp64: tau |d| <= 1e-9 (1 + |ref|);
+ * fd_ext residual |rnea(q, qd, qdd) - (tau + J^T f)| <= 1e-8 (1 + |tau + J^T f|) and qdd to
+ * 1e-7 (1 + |ref|); zero wrenches agree with the plain entry points to 1e-12 (1 + |ref|).  fp32
+ * against the fp64 kernel on the same fp32-rounded inputs, per configuration: rnea_ext
+ * max|d| <= 1e-4 (1 + max|ref|), fd_ext residual norm-wise <= 1e-3.  Measured (MI355X, B = 257,
+ * forces +-20 N, moments +-5 N m): fp64 tau 2.0e-14 FR3 / 1.6e-13 16 links / 1.0e-13 floating base;
+ * fd_ext residual 4.3e-12 and qdd 6.0e-11 at most (16 links); zero wrench 2.8e-13 at most; fp32
+ * rnea_ext 8.3e-7 (floating base), fd_ext residual 7.9e-6 (FR3). */
+int multibody_rnea_ext_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                 const float *fext, float *tau, int64_t batch, int64_t ld, void *stream);
+int multibody_rnea_ext_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                 const double *fext, double *tau, int64_t batch, int64_t ld, void *stream);
+int multibody_fd_ext_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                               const float *fext, float *qdd, int64_t batch, int64_t ld, void *stream);
+int multibody_fd_ext_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                               const double *fext, double *qdd, int64_t batch, int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch). */
+int multibody_rnea_ext_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                      const float *fext, float *tau, int64_t batch);
+int multibody_rnea_ext_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                      const double *fext, double *tau, int64_t batch);
+int multibody_fd_ext_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                    const float *fext, float *qdd, int64_t batch);
+int multibody_fd_ext_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                    const double *fext, double *qdd, int64_t batch);
+/* One configuration, fp64, caller-provided output of n doubles, on the calling thread: the same
+ * lane body compiled for the host, no GPU needed.  Serial revolute chains of a
+ * multibody_supported_dofs length on an FMA3 / AVX2 CPU; anything else (trees, prismatic joints, a
+ * floating base) RB_ERR_UNSUPPORTED.  fd_ext: the mass-matrix form up to 12 links, else the ABA. */
+int multibody_rnea_ext(const Multibody *mb, const double *q, const double *qd, const double *qdd, const double *fext,
+                       double *tau);
+int multibody_fd_ext(const Multibody *mb, const double *q, const double *qd, const double *tau, const double *fext,
+                     double *qdd);
+/* Inspection of those kernels (no kind number): fd != 0 selects fd_ext, else rnea_ext; otherwise as
+ * multibody_rollout_vjp_jit_source / _compile. */
+int multibody_ext_jit_source(const Multibody *mb, int fd, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_ext_jit_compile(const Multibody *mb, int fd, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

@@ -74,6 +74,7 @@ struct Multibody {
     rbamd::Model model;
     std::vector<float> pk32;
     std::vector<double> pk64;
+    std::vector<double> ra64;  // every link's axis frame (Model::axis_frames): the host external-wrench forms
     mutable rbamd::DeviceCache cache;  // constants and hipRTC kernels on the devices it has run on
 };
 
@@ -99,6 +100,7 @@ Multibody *make(rbamd::Model &&m) {
     Multibody *mb = new Multibody();
     mb->pk32 = m.pack_f32();
     mb->pk64 = m.pack_f64();
+    mb->ra64 = m.axis_frames();
     mb->model = std::move(m);
     return mb;
 }
@@ -284,6 +286,17 @@ hipError_t launch_rollout_vjp(const Multibody *mb, const T *q, const T *qd, cons
     void *args[] = {&q, &qd, &tau_seq, &dt, &K, &gq, &gqd, &g_q0, &g_qd0, &g_tau, &work, &B, &ld};
     return launch_any(mb, rbamd::JitKind::RolloutVjp, sizeof(T) == 8, B, false, s, args,
                       [&] { return no_generic(mb, "the rollout gradient runs"); });
+}
+
+// Dynamics under external link wrenches (ext_body.hip.hpp): model-specialised kernels only, SoA
+// rows, every model; fext has 6 n rows.
+template <typename T>
+hipError_t launch_ext(const Multibody *mb, bool fd, const T *q, const T *qd, const T *third, const T *fext, T *out,
+                      uint32_t B, int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    void *args[] = {&q, &qd, &third, &fext, &out, &B, &ld, &bs};
+    return launch_any(mb, fd ? rbamd::JitKind::FdExt : rbamd::JitKind::RneaExt, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the external-wrench dynamics run"); });
 }
 
 constexpr int64_t kChunk = int64_t(1) << 28;  // per-launch batch cap: b * sizeof(T) < 2^32
@@ -482,6 +495,31 @@ int idfd_batch(const Multibody *mb, const T *q, const T *qd, const T *qdd, const
         const int n = mb->model.n;
         return launch_idfd_any<T>(mb, mdl, at(q, n), at(qd, n), at(qdd, n), at(tau_in, n), at(tau, n), at(qdd_out, n),
                                   nb, ld, (hipStream_t)stream, tiled);
+    });
+}
+
+// The external-wrench entry points' own argument checks: every array present, the output none of
+// the inputs.  op: "rnea_ext" / "fd_ext".
+template <typename T>
+int ext_args_ok(const char *op, std::initializer_list<const T *> in, const T *out) {
+    if (!out) return set_err(RB_ERR_NULL, "NULL array");
+    for (const T *p : in)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    for (const T *p : in)
+        if (p == out) return set_err(RB_ERR_ARG, std::string(op) + ": an output array is also an input (no in-place form)");
+    return RB_OK;
+}
+
+// third: qdd (rnea_ext, out = tau) or tau (fd_ext, out = qdd)
+template <typename T>
+int ext_batch(const Multibody *mb, bool fd, const T *q, const T *qd, const T *third, const T *fext, T *out,
+              int64_t batch, int64_t ld, void *stream) {
+    auto args_ok = [&] { return ext_args_ok<T>(fd ? "fd_ext" : "rnea_ext", {q, qd, third, fext}, out); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, fd ? "fd_ext launch" : "rnea_ext launch",
+                         [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_ext<T>(mb, fd, at(q, n), at(qd, n), at(third, n), at(fext, 6 * n), at(out, n), nb, ld,
+                             (hipStream_t)stream);
     });
 }
 
@@ -730,6 +768,16 @@ int fd_deriv_host(const Multibody *mb, const T *q, const T *qd, const T *tau, T 
 }
 
 template <typename T>
+int ext_host(const Multibody *mb, bool fd, const T *q, const T *qd, const T *third, const T *fext, T *out,
+             int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call_rows<T, 4, 1>(mb, {q, qd, third, fext}, {n, n, n, 6 * n}, {out}, {n}, 0, false, batch, no_check,
+                                   [&](T **i, T **o, hipStream_t s) {
+        return ext_batch<T>(mb, fd, i[0], i[1], i[2], i[3], o[0], batch, batch, s);
+    });
+}
+
+template <typename T>
 int rollout_vjp_host(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
                      const T *gqd, T *g_q0, T *g_qd0, T *g_tau, int64_t batch) {
     // the step count comes before the arrays, as in the device form
@@ -969,6 +1017,14 @@ int64_t compile_query(const Multibody *mb, int kind, int f64, int64_t batch, int
     return (int64_t)code.size();
 }
 
+// The external-wrench kernels have no public kind number either: fd selects fd_ext (else rnea_ext).
+int check_ext_query(const Multibody *mb, int64_t batch) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (batch < 1) return set_err(RB_ERR_ARG, "batch must be positive");
+    return RB_OK;
+}
+int ext_kind(int fd) { return (int)(fd ? rbamd::JitKind::FdExt : rbamd::JitKind::RneaExt); }
+
 void note_jit_errors(const Multibody *mb) {
     for (std::string &err : mb->cache.jit_errors()) g_last_error = std::move(err);
 }
@@ -1024,6 +1080,15 @@ int64_t multibody_jit_compile_ex(const Multibody *mb, int kind, int f64, int64_t
 int64_t multibody_rollout_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch) {
     if (int rc = check_vjp_query(mb, batch)) return -rc;
     return compile_query(mb, (int)rbamd::JitKind::RolloutVjp, f64, batch, 0, arch);
+}
+
+int multibody_ext_jit_source(const Multibody *mb, int fd, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_ext_query(mb, batch), ext_kind(fd), f64, batch, 0, buf, cap);
+}
+
+int64_t multibody_ext_jit_compile(const Multibody *mb, int fd, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_ext_query(mb, batch)) return -rc;
+    return compile_query(mb, ext_kind(fd), f64, batch, 0, arch);
 }
 
 int multibody_upload(const Multibody *mb) {
@@ -1280,6 +1345,67 @@ int multibody_fd_deriv(const Multibody *mb, const double *q, const double *qd, c
         return set_err(RB_ERR_UNSUPPORTED, "fd_deriv: the single-configuration form runs on the host and needs an "
                                            "FMA3 / AVX2 CPU");
     return RB_OK;
+}
+
+// ------------------------------------------------------------- external link wrenches
+int multibody_rnea_ext_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                 const float *fext, float *tau, int64_t batch, int64_t ld, void *stream) {
+    return ext_batch<float>(mb, false, q, qd, qdd, fext, tau, batch, ld, stream);
+}
+int multibody_rnea_ext_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                 const double *fext, double *tau, int64_t batch, int64_t ld, void *stream) {
+    return ext_batch<double>(mb, false, q, qd, qdd, fext, tau, batch, ld, stream);
+}
+int multibody_fd_ext_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                               const float *fext, float *qdd, int64_t batch, int64_t ld, void *stream) {
+    return ext_batch<float>(mb, true, q, qd, tau, fext, qdd, batch, ld, stream);
+}
+int multibody_fd_ext_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                               const double *fext, double *qdd, int64_t batch, int64_t ld, void *stream) {
+    return ext_batch<double>(mb, true, q, qd, tau, fext, qdd, batch, ld, stream);
+}
+int multibody_rnea_ext_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                      const float *fext, float *tau, int64_t batch) {
+    return ext_host<float>(mb, false, q, qd, qdd, fext, tau, batch);
+}
+int multibody_rnea_ext_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                      const double *fext, double *tau, int64_t batch) {
+    return ext_host<double>(mb, false, q, qd, qdd, fext, tau, batch);
+}
+int multibody_fd_ext_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                    const float *fext, float *qdd, int64_t batch) {
+    return ext_host<float>(mb, true, q, qd, tau, fext, qdd, batch);
+}
+int multibody_fd_ext_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                    const double *fext, double *qdd, int64_t batch) {
+    return ext_host<double>(mb, true, q, qd, tau, fext, qdd, batch);
+}
+
+// Single configuration, fp64, on the calling thread (host_eval.cpp): serial revolute chains of a
+// multibody_supported_dofs length.
+static int ext_single(const Multibody *mb, bool fd, const double *q, const double *qd, const double *third,
+                      const double *fext, double *out) {
+    const char *op = fd ? "fd_ext" : "rnea_ext";
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = ext_args_ok<double>(op, {q, qd, third, fext}, out)) return rc;
+    if (!mb->model.serial_revolute())
+        return set_err(RB_ERR_UNSUPPORTED, std::string(op) + ": the single-configuration form evaluates serial revolute "
+                                           "chains only (kinematic trees, prismatic joints and a floating base take "
+                                           "the batched entry points)");
+    const bool ok = fd ? rbamd::host_fd_ext(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, third, fext, out)
+                       : rbamd::host_rnea_ext(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, third, fext, out);
+    if (!ok)
+        return set_err(RB_ERR_UNSUPPORTED, std::string(op) + ": the single-configuration form runs on the host and "
+                                           "needs an FMA3 / AVX2 CPU");
+    return RB_OK;
+}
+int multibody_rnea_ext(const Multibody *mb, const double *q, const double *qd, const double *qdd, const double *fext,
+                       double *tau) {
+    return ext_single(mb, false, q, qd, qdd, fext, tau);
+}
+int multibody_fd_ext(const Multibody *mb, const double *q, const double *qd, const double *tau, const double *fext,
+                     double *qdd) {
+    return ext_single(mb, true, q, qd, tau, fext, qdd);
 }
 
 // ------------------------------------------------------------- batched (host)

@@ -18,6 +18,7 @@
 #include "rollout_vjp_body.hip.hpp"  // first: rnea_deriv_body declares the host reciprocal fdh_body's L D L^T takes
 #include "crba_body.hip.hpp"
 #include "dofs.hpp"
+#include "ext_body.hip.hpp"
 #include "kernels.hpp"
 #include "rnea_body.hip.hpp"
 
@@ -208,6 +209,64 @@ RB_HOST_FMA bool rollout_vjp_fma(int n, const double *mdl, const double *q, cons
     }
 }
 
+RB_HOST_FMA bool rnea_ext_fma(int n, const double *mdl, const double *ra, const double *q, const double *qd,
+                              const double *qdd, const double *fext, double *tau) {
+    switch (n) {
+#define X(N)                                                                                        \
+    case N: {                                                                                       \
+        double a[N], b[N], c[N];                                                                    \
+        for (int j = 0; j < N; ++j) {                                                               \
+            a[j] = q[j];                                                                            \
+            b[j] = qd[j];                                                                           \
+            c[j] = qdd[j];                                                                          \
+        }                                                                                           \
+        dev::rnea_ext_eval<double, N, false, HostSerialTopo<N>>(                                    \
+            mdl, ra, a, b, c, [&](int r) { return fext[r]; }, [&](int j, double v) { tau[j] = v; }); \
+        return true;                                                                                \
+    }
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
+// The mass-matrix form up to kHostFdDerivMaxLinks links, the ABA beyond (the fd_form policy's
+// default; the tuning knob is not read here).
+template <int N>
+RB_HOST_FMA bool fd_ext_fma_n(const double *mdl, const double *ra, const double *q, const double *qd,
+                              const double *tau, const double *fext, double *qdd) {
+    double a[N], b[N], t[N];
+    for (int j = 0; j < N; ++j) {
+        a[j] = q[j];
+        b[j] = qd[j];
+        t[j] = tau[j];
+    }
+    auto fx = [&](int r) { return fext[r]; };
+    auto out = [&](int j, double v) { qdd[j] = v; };
+    if constexpr (N <= kHostFdDerivMaxLinks) {
+        dev::fdh_ext_eval<double, N, false, HostSerialTopo<N>>(
+            mdl, ra, a, b, fx,
+            [&](double(&tv)[N]) {
+                for (int j = 0; j < N; ++j) tv[j] = t[j];
+            },
+            out);
+    } else {
+        dev::aba_ext_eval<double, N, false, HostSerialTopo<N>>(mdl, ra, a, b, t, fx, out);
+    }
+    return true;
+}
+
+RB_HOST_FMA bool fd_ext_fma(int n, const double *mdl, const double *ra, const double *q, const double *qd,
+                            const double *tau, const double *fext, double *qdd) {
+    switch (n) {
+#define X(N) \
+    case N: return fd_ext_fma_n<N>(mdl, ra, q, qd, tau, fext, qdd);
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -250,6 +309,16 @@ bool host_rollout_vjp(const Model &m, const double *pk, const double *q, const d
     if (!host_eval_supported(m) || m.n > kHostFdDerivMaxLinks || K < 1) return false;
     std::vector<double> work((size_t)K * 2 * m.n);
     return rollout_vjp_fma(m.n, pk, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work.data());
+}
+
+bool host_rnea_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                   const double *qdd, const double *fext, double *tau) {
+    return host_eval_supported(m) && rnea_ext_fma(m.n, pk, ra, q, qd, qdd, fext, tau);
+}
+
+bool host_fd_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                 const double *tau, const double *fext, double *qdd) {
+    return host_eval_supported(m) && fd_ext_fma(m.n, pk, ra, q, qd, tau, fext, qdd);
 }
 
 }  // namespace rbamd

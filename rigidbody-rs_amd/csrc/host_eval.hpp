@@ -34,4 +34,12 @@ bool host_rollout_vjp(const Model &m, const double *pk, const double *q, const d
                       double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
                       double *g_tau);
 
+// Dynamics under external link wrenches (ext_body.hip.hpp): fext [6 n] (link j's force, then its
+// moment, in its URDF link frame), ra = Model::axis_frames().  host_fd_ext: the mass-matrix form up
+// to kHostFdDerivMaxLinks links, the ABA beyond.
+bool host_rnea_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                   const double *qdd, const double *fext, double *tau);
+bool host_fd_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                 const double *tau, const double *fext, double *qdd);
+
 }  // namespace rbamd

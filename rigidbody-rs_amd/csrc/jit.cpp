@@ -46,8 +46,10 @@ std::string literal(double x, bool f64) {
 // and compile flags are made of.  Every tuning knob read here is part of jit_key.
 
 int jit_nt(JitKind kind) {
-    if (kind == JitKind::Rnea) return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
-    if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd) return tuning().fd_nt & 3;
+    // (the external-wrench kinds follow their plain neighbours: every row is touched once)
+    if (kind == JitKind::Rnea || kind == JitKind::RneaExt) return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
+    if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt)
+        return tuning().fd_nt & 3;
     const int v = tuning().kin_nt;  // CRBA, fwd_kin, jac
     if (v >= 0) return v & 3;
     return kind == JitKind::FwdKin ? 3 : 2;  // 7 rows in / 3 out: non-temporal loads pay too
@@ -322,6 +324,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const int pack = v.pack;
     const bool deriv = kind == JitKind::RneaDeriv || kind == JitKind::FdDeriv;
     const bool vjp = kind == JitKind::RolloutVjp;  // the rollout's adjoint: fd_deriv's scope and link forces
+    const bool ext = kind == JitKind::RneaExt || kind == JitKind::FdExt;  // external link wrenches (ext_body.hip.hpp)
     if ((deriv || vjp) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
@@ -364,7 +367,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     // 131 instead of 125 VGPRs (3 waves/SIMD instead of 4), and all its grid forms (pairs,
     // single tail, one per lane below 2^19) must stay bit-identical to each other.
     const bool dyn = kind == JitKind::Rnea || kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd ||
-                     deriv || vjp;
+                     deriv || vjp || ext;
     // jit_variant bit 16384 (A/B): the centre-of-mass form for the fp64 RNEA too
     // rnea_lane_rev: the fp64 RNEA of serial chains longer than 8 links, whose per-link forces
     // hold one wave per SIMD (12 links 264 VGPRs, 30 links 496) and do not fit LDS either
@@ -442,7 +445,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         }
         o << "};\n";
     }
-    o << (vjp                                               ? "#include \"rollout_vjp_body.hip.hpp\"\n"
+    o << (ext                                               ? "#include \"ext_body.hip.hpp\"\n"
+          : vjp                                             ? "#include \"rollout_vjp_body.hip.hpp\"\n"
           : deriv                                           ? "#include \"rnea_deriv_body.hip.hpp\"\n"
           : kind == JitKind::Rnea                             ? "#include \"rnea_body.hip.hpp\"\n"
           : fdh                                               ? "#include \"fdh_body.hip.hpp\"\n"
@@ -481,6 +485,12 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         for (size_t k = 0; k < pk.size(); ++k) o << "  " << literal(pk[k], f64) << ",\n";
     }
     o << "};\n";
+    if (ext) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
+        const std::vector<double> ra = m.axis_frames();
+        o << "static __device__ constexpr T kExtRa[" << ra.size() << "] = {\n";
+        for (size_t k = 0; k < ra.size(); ++k) o << "  " << literal(snap(ra[k]), f64) << ",\n";
+        o << "};\n";
+    }
     // ---- the kernel: one signature helper, one prologue per lane form
     const std::string head = std::string("extern \"C\" __global__ __launch_bounds__(256) ") +
                              (waves ? "__attribute__((amdgpu_waves_per_eu(" + std::to_string(waves) + "))) " : "") + "void ";
@@ -585,6 +595,19 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         } else {
             o << lane_prologue << "  rbamd::dev::aba_lane<T, N, " << F << ", Topo>" << lane_args;
         }
+    } else if (ext) {
+        // one configuration per lane on SoA rows; fext [6 N][ld] sits between the inputs and the output
+        const bool fd = kind == JitKind::FdExt;
+        sig(std::string("const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ ") +
+            (fd ? "tau" : "qdd") + ", const T *__restrict__ fext, T *__restrict__ " + (fd ? "qdd" : "tau") +
+            ", uint32_t B, int64_t ld, int64_t bs");
+        o << lane_prologue;
+        if (fd)
+            o << "  rbamd::dev::fd_ext_lane<T, N, " << F << ", Topo, " << (jit_fd_form(m) == 2 ? "true" : "false")
+              << ">(kModel, kExtRa, q + o, qd + o, tau + o, fext + o, qdd + o, threadIdx.x, ld);\n}\n";
+        else
+            o << "  rbamd::dev::rnea_ext_lane<T, N, " << F
+              << ", Topo>(kModel, kExtRa, q + o, qd + o, qdd + o, fext + o, tau + o, threadIdx.x, ld);\n}\n";
     } else if (deriv) {
         // one configuration per lane on SoA rows; a NULL output is neither evaluated nor stored
         const bool fd = kind == JitKind::FdDeriv;

@@ -33,11 +33,14 @@ namespace rbamd {
 // RolloutVjp: the reverse-mode gradient of the fused rollout (rollout_vjp_body.hip.hpp), FdDeriv's
 // scope, hipRTC only.  Internal: the public kind numbers of the *_ex inspection queries end at 8
 // (kJitPublicKinds); this kernel is inspected through multibody_rollout_vjp_jit_source / _compile.
+// RneaExt / FdExt: inverse / forward dynamics under external link wrenches (ext_body.hip.hpp), every
+// model, hipRTC only, one configuration per lane on SoA rows; FdExt takes the formulation
+// jit_fd_form picks for Fd.  Internal too: multibody_ext_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
-    RolloutVjp = 9
+    RolloutVjp = 9, RneaExt = 10, FdExt = 11
 };
-constexpr int kJitKinds = 10;
+constexpr int kJitKinds = 12;
 constexpr int kJitPublicKinds = 9;
 
 // Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds and the

@@ -503,6 +503,12 @@ std::vector<T> pack(const Model &m) {
 }
 }  // namespace
 
+std::vector<double> Model::axis_frames() const {
+    std::vector<double> out((size_t)n * 9);
+    for (int i = 0; i < n; ++i) axis_frame(links[i].axis, &out[(size_t)i * 9]);
+    return out;
+}
+
 std::vector<float> Model::pack_f32() const { return pack<float>(*this); }
 std::vector<double> Model::pack_f64() const { return pack<double>(*this); }
 

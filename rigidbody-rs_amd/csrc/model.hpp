@@ -83,6 +83,10 @@ struct Model {
     // c' = R_a^T c, I' = R_a^T I R_a -- so the kernels' z-joint code is exact for any axis.
     std::vector<float> pack_f32() const;
     std::vector<double> pack_f64() const;
+    // Every link's R_a of the packing above (9 n, row-major; x_urdf = R_a x_kernel): what turns a
+    // vector given in a link's URDF frame into the kernels' frame of that link (ext_body.hip.hpp).
+    // The packed block keeps only the last link's (kTailOut).
+    std::vector<double> axis_frames() const;
 };
 
 // nalgebra-equivalent helpers (also used for unit tests through the C ABI-free path).

@@ -95,13 +95,20 @@ _SIGNATURES = {
     # inspection of the rollout gradient's kernel: (handle, f64, batch, ...)
     "multibody_rollout_vjp_jit_source": (_int, [_vp, _int, _i64, _str, _i64]),
     "multibody_rollout_vjp_jit_compile": (_i64, [_vp, _int, _i64, _str]),
+    # external link wrenches: one configuration (handle, q, qd, qdd | tau, fext, out); inspection
+    # (handle, fd, f64, batch, ...)
+    "multibody_rnea_ext": (_int, [_vp] + [_dp] * 5),
+    "multibody_fd_ext": (_int, [_vp] + [_dp] * 5),
+    "multibody_ext_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
+    "multibody_ext_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
 }
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
-_ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7}
+_ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7,
+           "rnea_ext": 5, "fd_ext": 5}
 for _t in ("f32", "f64"):
     for _k, _n in _ARRAYS.items():
         _SIGNATURES[f"multibody_{_k}_batch_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _i64, _vp])
-        if not _k.endswith("_deriv"):
+        if not _k.endswith(("_deriv", "_ext")):
             _SIGNATURES[f"multibody_{_k}_batch_tiled_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _vp])
         if _k not in ("crba", "fwd_kin", "jac"):
             _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
@@ -427,6 +434,87 @@ class Multibody:
         if r < 0:
             raise RigidBodyError(last_error())
         return r
+
+    # ---- external link wrenches: fext holds link j's force then its moment, in its URDF link frame
+    def rnea_ext(self, q, qd, qdd, fext) -> np.ndarray:
+        """multibody_rnea_ext: tau = rnea(q, qd, qdd) - sum_j J_j^T fext_j; fext [6 n] (or [n, 6]).  One
+        configuration, on the calling thread."""
+        return self._ext_single(_lib.multibody_rnea_ext, "rnea_ext", q, qd, qdd, fext)
+
+    def fd_ext(self, q, qd, tau, fext) -> np.ndarray:
+        """multibody_fd_ext: qdd = fd(q, qd, tau + sum_j J_j^T fext_j); as rnea_ext."""
+        return self._ext_single(_lib.multibody_fd_ext, "fd_ext", q, qd, tau, fext)
+
+    def _ext_single(self, fn, what, q, qd, third, fext):
+        q, qd, third = (_dvec(x, self.n) for x in (q, qd, third))
+        fext = _dvec(np.asarray(fext, dtype=np.float64).reshape(-1), 6 * self.n)
+        out = np.empty(self.n)
+        _check(fn(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, third, fext, out)]), what)
+        return out
+
+    def ext_jit_source(self, fd=False, f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the rnea_ext (fd=False) / fd_ext (fd=True) kernel (multibody_ext_jit_source)."""
+        a = (self._h, int(bool(fd)), int(bool(f64)), int(batch))
+        n = _lib.multibody_ext_jit_source(*a, None, 0)
+        if n < 0:
+            raise RigidBodyError(last_error())
+        buf = ctypes.create_string_buffer(n + 1)
+        _lib.multibody_ext_jit_source(*a, buf, n + 1)
+        return buf.value.decode()
+
+    def ext_jit_compile(self, fd=False, f64=False, arch="gfx950", batch=1 << 20) -> int:
+        r = _lib.multibody_ext_jit_compile(self._h, int(bool(fd)), int(bool(f64)), int(batch), arch.encode())
+        if r < 0:
+            raise RigidBodyError(last_error())
+        return r
+
+    def _ext_call(self, kind, q, qd, third, third_name, fext, out, out_name, stream):
+        q = _soa(q, self.n, "q")
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        qd = _soa(qd, self.n, "qd", q.dtype, B)
+        third = _soa(third, self.n, third_name, q.dtype, B)
+        fext = _soa(fext, 6 * self.n, "fext", q.dtype, B)
+        if out is None:
+            out = torch.empty((self.n, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
+        else:
+            _soa(out, self.n, out_name, q.dtype, B)
+        live = (q, qd, third, fext, out)
+        ld = _same_ld(live)
+        dev = _one_device(live)
+        fn = getattr(_lib, f"multibody_{kind}_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, *[t.data_ptr() for t in live], B, ld, _stream_ptr(stream, dev)), f"{kind}_batch")
+        return out
+
+    def rnea_ext_batch(self, q, qd, qdd, fext, out=None, stream=None):
+        """multibody_rnea_ext_batch_*: q, qd, qdd [n, B], fext [6 n, B] (row 6 j + c: component c of
+        the wrench on link j, force then moment, in link j's URDF frame) -> tau [n, B]."""
+        return self._ext_call("rnea_ext", q, qd, qdd, "qdd", fext, out, "tau", stream)
+
+    def fd_ext_batch(self, q, qd, tau, fext, out=None, stream=None):
+        """multibody_fd_ext_batch_*: as rnea_ext_batch -> qdd [n, B]."""
+        return self._ext_call("fd_ext", q, qd, tau, "tau", fext, out, "qdd", stream)
+
+    def _ext_host(self, kind, q, qd, third, fext, dtype):
+        arrs = _host_soa((q, qd, third), self.n, dtype)
+        B = arrs[0].shape[1]
+        fext = np.ascontiguousarray(fext, dtype=arrs[0].dtype)
+        if fext.shape != (6 * self.n, B):
+            raise ValueError(f"fext must be [{6 * self.n}, {B}], got {fext.shape}")
+        out = np.empty((self.n, B), dtype=arrs[0].dtype)
+        fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if out.dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in (*arrs, fext, out)], B), f"{kind}_batch_host")
+        return out
+
+    def rnea_ext_batch_host(self, q, qd, qdd, fext, dtype=np.float64):
+        """Blocking host form of rnea_ext_batch on numpy arrays."""
+        return self._ext_host("rnea_ext", q, qd, qdd, fext, dtype)
+
+    def fd_ext_batch_host(self, q, qd, tau, fext, dtype=np.float64):
+        """Blocking host form of fd_ext_batch on numpy arrays."""
+        return self._ext_host("fd_ext", q, qd, tau, fext, dtype)
 
     # ------------------------------------------------------- batched, device [n, B]
     def _soa_call(self, kind, ins, outs, stream):
