@@ -510,6 +510,83 @@ int multibody_fd_ext(const Multibody *mb, const double *q, const double *qd, con
 int multibody_ext_jit_source(const Multibody *mb, int fd, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_ext_jit_compile(const Multibody *mb, int fd, int f64, int64_t batch, const char *arch);
 
+/* ---- kinematics of every link --------------------------------------------------- */
+/* Pose and spatial velocity of EVERY link (multibody_fwd_kin / multibody_jac answer for the last
+ * link only, and without an orientation): what a caller needs to form the wrenches fext of the
+ * entry points above -- where a foot's frame is, how it is oriented, how fast its origin moves.
+ *
+ * Frame: link j's own URDF link frame -- the joint's child frame, after the joint's motion; the
+ * frame fext_j is given in, and the frame multibody_fwd_kin / multibody_jac report for the last
+ * link.  With RB_MODEL_GENERAL_AXES (and the tree reading) the kernels sweep in their own per-link
+ * frames and turn the results on the way out; a caller never sees that frame.
+ *
+ * Layout (SoA rows of leading dimension ld, configuration b):
+ *   pos [3 n][ld]  pos[(3 j + c) * ld + b]: component c of the frame origin, in the base frame
+ *   rot [9 n][ld]  rot[(9 j + e) * ld + b], e = row + 3 * col (column-major, the ABI's order): the
+ *                  rotation R_j with x_base = R_j x_link
+ *   vel [6 n][ld]  rows 6 j + 0..2 the linear velocity of the frame origin, rows 6 j + 3..5 the
+ *                  angular velocity, both expressed in link j's frame -- the [lin; rot] row order of
+ *                  the Jacobian and of fext: vel_j = J_j(q) qd with J_j the body Jacobian of link j,
+ *                  so sum_j fext_j . vel_j is the power the wrenches deliver.  Purely kinematic: the
+ *                  reference's gravity-as-base-acceleration does not enter.
+ * q, qd are [n][ld].  The six virtual links of a floating base have rows like any other link.  The
+ * single-configuration forms take pos [3 n], rot [9 n], vel [6 n].
+ *
+ * Algorithm (link_kin_body.hip.hpp): one root-to-leaf sweep, one configuration per lane; a link's
+ * rows are stored as soon as the link completes.  Only a link with more than one child is kept
+ * beyond the next step of the sweep (a serial chain keeps one pose / velocity, a quadruped its
+ * trunk's too).
+ *
+ * Scope: every model the model-specialised kernels run -- serial chains under the reference's
+ * reading or with general axes, of every supported length; kinematic trees; prismatic joints; a
+ * floating base.  Model-specialised (hipRTC) kernels only, no kind number: with hipRTC disabled or
+ * failed RB_ERR_UNSUPPORTED with the log.  SoA rows only (no tiled form), batches split at 2^28
+ * per launch.
+ *
+ * Checks, in order: handle (RB_ERR_NULL), batch >= 0, ld >= batch (RB_ERR_ARG), batch == 0 (RB_OK,
+ * nothing else looked at), a NULL array (RB_ERR_NULL; every array is required), an output passed as
+ * one of the inputs or as the other output (RB_ERR_ARG), then hipRTC.
+ *
+ * Input domain: as above: a configuration with a NaN / Inf in q or qd, or an angle past the bound,
+ * gets NaN in every element of every output; the others are unaffected.  Every input is checked
+ * before the configuration's first row is stored.
+ *
+ * Accuracy (tests/test_link_kin_host.py, tests/test_gpu_link_kin.py; reference tests/link_kin_ref.py:
+ * world poses accumulated root to leaf from the 6x6 Featherstone model's own joint transforms,
+ * velocities from v_j = X_j v_parent + S_j qd_j).  fp64: every element of pos, rot, vel
+ * |d| <= 1e-9 (1 + |ref|), the fwd_kin / jac contract; the last link's pos / vel agree with
+ * multibody_fwd_kin / multibody_jac . qd to 1e-12 (1 + |ref|); rot is orthonormal to 1e-12; and
+ * sum_j fext_j . vel_j = qd . (rnea - rnea_ext) to 1e-8 (1 + sum_j |fext_j . vel_j|).  fp32 against
+ * the fp64 kernel on the same fp32-rounded inputs, per configuration and output array:
+ * max|d| <= 1e-4 (1 + max|ref|).  Measured (MI355X, B = 257): fp64 9.3e-16 FR3 / 2.1e-15 16 links /
+ * 1.8e-15 five links with general axes / 1.8e-15 the 9-joint tree / 2.6e-15 floating base; the
+ * power identity 1.1e-15 at most; |q| ~ 2^40 rad 1.4e-15; fp32 2.7e-7 at most (floating base, vel).
+ * Single-configuration forms on the host: 4.8e-16 FR3, 4.1e-15 at most (30 links). */
+int multibody_link_pose_batch_f32(const Multibody *mb, const float *q, float *pos, float *rot, int64_t batch,
+                                  int64_t ld, void *stream);
+int multibody_link_pose_batch_f64(const Multibody *mb, const double *q, double *pos, double *rot, int64_t batch,
+                                  int64_t ld, void *stream);
+int multibody_link_vel_batch_f32(const Multibody *mb, const float *q, const float *qd, float *vel, int64_t batch,
+                                 int64_t ld, void *stream);
+int multibody_link_vel_batch_f64(const Multibody *mb, const double *q, const double *qd, double *vel, int64_t batch,
+                                 int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch). */
+int multibody_link_pose_batch_host_f32(const Multibody *mb, const float *q, float *pos, float *rot, int64_t batch);
+int multibody_link_pose_batch_host_f64(const Multibody *mb, const double *q, double *pos, double *rot, int64_t batch);
+int multibody_link_vel_batch_host_f32(const Multibody *mb, const float *q, const float *qd, float *vel, int64_t batch);
+int multibody_link_vel_batch_host_f64(const Multibody *mb, const double *q, const double *qd, double *vel,
+                                      int64_t batch);
+/* One configuration, fp64, caller-provided outputs, on the calling thread: the same lane body
+ * compiled for the host, no GPU needed.  Serial revolute chains of a multibody_supported_dofs length
+ * on an FMA3 / AVX2 CPU; anything else (trees, prismatic joints, a floating base)
+ * RB_ERR_UNSUPPORTED -- the scope of multibody_rnea_ext. */
+int multibody_link_pose(const Multibody *mb, const double *q, double *pos, double *rot);
+int multibody_link_vel(const Multibody *mb, const double *q, const double *qd, double *vel);
+/* Inspection of those kernels (no kind number): vel != 0 selects link_vel, else link_pose; otherwise
+ * as multibody_ext_jit_source / _compile. */
+int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_link_kin_jit_compile(const Multibody *mb, int vel, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

@@ -299,6 +299,25 @@ hipError_t launch_ext(const Multibody *mb, bool fd, const T *q, const T *qd, con
                       [&] { return no_generic(mb, "the external-wrench dynamics run"); });
 }
 
+// Kinematics of every link (link_kin_body.hip.hpp): model-specialised kernels only, SoA rows, every
+// model; pos has 3 n rows, rot 9 n, vel 6 n.
+template <typename T>
+hipError_t launch_link_pose(const Multibody *mb, const T *q, T *pos, T *rot, uint32_t B, int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    void *args[] = {&q, &pos, &rot, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::LinkPose, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the link kinematics run"); });
+}
+
+template <typename T>
+hipError_t launch_link_vel(const Multibody *mb, const T *q, const T *qd, T *vel, uint32_t B, int64_t ld,
+                           hipStream_t s) {
+    int64_t bs = 256;
+    void *args[] = {&q, &qd, &vel, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::LinkVel, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the link kinematics run"); });
+}
+
 constexpr int64_t kChunk = int64_t(1) << 28;  // per-launch batch cap: b * sizeof(T) < 2^32
 
 int check_batch(const Multibody *mb, int64_t batch, int64_t ld) {
@@ -575,6 +594,35 @@ int fd_deriv_batch(const Multibody *mb, const T *q, const T *qd, const T *tau, T
     });
 }
 
+// The link-kinematics entry points' own argument checks: every array present, no output that is
+// also an input or the other output.  vel: link_vel (else link_pose); every model is in scope.
+template <typename T>
+int link_kin_args_ok(const Multibody *mb, bool vel, std::initializer_list<const T *> in,
+                     std::initializer_list<const T *> out) {
+    for (const T *p : out)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    return deriv_args_ok<T>(mb, vel ? rbamd::JitKind::LinkVel : rbamd::JitKind::LinkPose, vel ? "link_vel" : "link_pose",
+                            in, out);
+}
+
+template <typename T>
+int link_pose_batch(const Multibody *mb, const T *q, T *pos, T *rot, int64_t batch, int64_t ld, void *stream) {
+    auto args_ok = [&] { return link_kin_args_ok<T>(mb, false, {q}, {pos, rot}); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "link_pose launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_link_pose<T>(mb, at(q, n), at(pos, 3 * n), at(rot, 9 * n), nb, ld, (hipStream_t)stream);
+    });
+}
+
+template <typename T>
+int link_vel_batch(const Multibody *mb, const T *q, const T *qd, T *vel, int64_t batch, int64_t ld, void *stream) {
+    auto args_ok = [&] { return link_kin_args_ok<T>(mb, true, {q, qd}, {vel}); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "link_vel launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_link_vel<T>(mb, at(q, n), at(qd, n), at(vel, 6 * n), nb, ld, (hipStream_t)stream);
+    });
+}
+
 template <typename T>
 int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt, int K, T *traj, int64_t batch,
                   int64_t ld, void *stream) {
@@ -775,6 +823,24 @@ int ext_host(const Multibody *mb, bool fd, const T *q, const T *qd, const T *thi
                                    [&](T **i, T **o, hipStream_t s) {
         return ext_batch<T>(mb, fd, i[0], i[1], i[2], i[3], o[0], batch, batch, s);
     });
+}
+
+template <typename T>
+int link_pose_host(const Multibody *mb, const T *q, T *pos, T *rot, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call_rows<T, 1, 2>(
+        mb, {q}, {n}, {pos, rot}, {3 * n, 9 * n}, 0, false, batch,
+        [&] { return link_kin_args_ok<T>(mb, false, {q}, {pos, rot}); },
+        [&](T **i, T **o, hipStream_t s) { return link_pose_batch<T>(mb, i[0], o[0], o[1], batch, batch, s); });
+}
+
+template <typename T>
+int link_vel_host(const Multibody *mb, const T *q, const T *qd, T *vel, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call_rows<T, 2, 1>(
+        mb, {q, qd}, {n, n}, {vel}, {6 * n}, 0, false, batch,
+        [&] { return link_kin_args_ok<T>(mb, true, {q, qd}, {vel}); },
+        [&](T **i, T **o, hipStream_t s) { return link_vel_batch<T>(mb, i[0], i[1], o[0], batch, batch, s); });
 }
 
 template <typename T>
@@ -1024,6 +1090,8 @@ int check_ext_query(const Multibody *mb, int64_t batch) {
     return RB_OK;
 }
 int ext_kind(int fd) { return (int)(fd ? rbamd::JitKind::FdExt : rbamd::JitKind::RneaExt); }
+// ... nor the link-kinematics kernels (check_ext_query's checks): vel selects link_vel (else link_pose).
+int link_kin_kind(int vel) { return (int)(vel ? rbamd::JitKind::LinkVel : rbamd::JitKind::LinkPose); }
 
 void note_jit_errors(const Multibody *mb) {
     for (std::string &err : mb->cache.jit_errors()) g_last_error = std::move(err);
@@ -1089,6 +1157,15 @@ int multibody_ext_jit_source(const Multibody *mb, int fd, int f64, int64_t batch
 int64_t multibody_ext_jit_compile(const Multibody *mb, int fd, int f64, int64_t batch, const char *arch) {
     if (int rc = check_ext_query(mb, batch)) return -rc;
     return compile_query(mb, ext_kind(fd), f64, batch, 0, arch);
+}
+
+int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_ext_query(mb, batch), link_kin_kind(vel), f64, batch, 0, buf, cap);
+}
+
+int64_t multibody_link_kin_jit_compile(const Multibody *mb, int vel, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_ext_query(mb, batch)) return -rc;
+    return compile_query(mb, link_kin_kind(vel), f64, batch, 0, arch);
 }
 
 int multibody_upload(const Multibody *mb) {
@@ -1406,6 +1483,65 @@ int multibody_rnea_ext(const Multibody *mb, const double *q, const double *qd, c
 int multibody_fd_ext(const Multibody *mb, const double *q, const double *qd, const double *tau, const double *fext,
                      double *qdd) {
     return ext_single(mb, true, q, qd, tau, fext, qdd);
+}
+
+// ------------------------------------------------------------- kinematics of every link
+int multibody_link_pose_batch_f32(const Multibody *mb, const float *q, float *pos, float *rot, int64_t batch,
+                                  int64_t ld, void *stream) {
+    return link_pose_batch<float>(mb, q, pos, rot, batch, ld, stream);
+}
+int multibody_link_pose_batch_f64(const Multibody *mb, const double *q, double *pos, double *rot, int64_t batch,
+                                  int64_t ld, void *stream) {
+    return link_pose_batch<double>(mb, q, pos, rot, batch, ld, stream);
+}
+int multibody_link_vel_batch_f32(const Multibody *mb, const float *q, const float *qd, float *vel, int64_t batch,
+                                 int64_t ld, void *stream) {
+    return link_vel_batch<float>(mb, q, qd, vel, batch, ld, stream);
+}
+int multibody_link_vel_batch_f64(const Multibody *mb, const double *q, const double *qd, double *vel, int64_t batch,
+                                 int64_t ld, void *stream) {
+    return link_vel_batch<double>(mb, q, qd, vel, batch, ld, stream);
+}
+int multibody_link_pose_batch_host_f32(const Multibody *mb, const float *q, float *pos, float *rot, int64_t batch) {
+    return link_pose_host<float>(mb, q, pos, rot, batch);
+}
+int multibody_link_pose_batch_host_f64(const Multibody *mb, const double *q, double *pos, double *rot, int64_t batch) {
+    return link_pose_host<double>(mb, q, pos, rot, batch);
+}
+int multibody_link_vel_batch_host_f32(const Multibody *mb, const float *q, const float *qd, float *vel,
+                                      int64_t batch) {
+    return link_vel_host<float>(mb, q, qd, vel, batch);
+}
+int multibody_link_vel_batch_host_f64(const Multibody *mb, const double *q, const double *qd, double *vel,
+                                      int64_t batch) {
+    return link_vel_host<double>(mb, q, qd, vel, batch);
+}
+
+// Single configuration, fp64, on the calling thread (host_eval.cpp): serial revolute chains of a
+// multibody_supported_dofs length.
+static int link_kin_single(const Multibody *mb, bool vel, const double *q, const double *qd, double *out0,
+                           double *out1) {
+    const char *op = vel ? "link_vel" : "link_pose";
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = vel ? link_kin_args_ok<double>(mb, true, {q, qd}, {out0})
+                     : link_kin_args_ok<double>(mb, false, {q}, {out0, out1}))
+        return rc;
+    if (!mb->model.serial_revolute())
+        return set_err(RB_ERR_UNSUPPORTED, std::string(op) + ": the single-configuration form evaluates serial revolute "
+                                           "chains only (kinematic trees, prismatic joints and a floating base take "
+                                           "the batched entry points)");
+    const bool ok = vel ? rbamd::host_link_vel(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, out0)
+                        : rbamd::host_link_pose(mb->model, mb->pk64.data(), mb->ra64.data(), q, out0, out1);
+    if (!ok)
+        return set_err(RB_ERR_UNSUPPORTED, std::string(op) + ": the single-configuration form runs on the host and "
+                                           "needs an FMA3 / AVX2 CPU");
+    return RB_OK;
+}
+int multibody_link_pose(const Multibody *mb, const double *q, double *pos, double *rot) {
+    return link_kin_single(mb, false, q, nullptr, pos, rot);
+}
+int multibody_link_vel(const Multibody *mb, const double *q, const double *qd, double *vel) {
+    return link_kin_single(mb, true, q, qd, vel, nullptr);
 }
 
 // ------------------------------------------------------------- batched (host)

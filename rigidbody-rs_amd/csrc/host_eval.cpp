@@ -20,6 +20,7 @@
 #include "dofs.hpp"
 #include "ext_body.hip.hpp"
 #include "kernels.hpp"
+#include "link_kin_body.hip.hpp"
 #include "rnea_body.hip.hpp"
 
 namespace rbamd {
@@ -267,6 +268,42 @@ RB_HOST_FMA bool fd_ext_fma(int n, const double *mdl, const double *ra, const do
     }
 }
 
+RB_HOST_FMA bool link_pose_fma(int n, const double *mdl, const double *ra, const double *q, double *pos, double *rot) {
+    switch (n) {
+#define X(N)                                                                                        \
+    case N: {                                                                                       \
+        double a[N];                                                                                \
+        for (int j = 0; j < N; ++j) a[j] = q[j];                                                    \
+        dev::link_pose_eval<double, N, false, HostSerialTopo<N>>(                                   \
+            mdl, ra, a, [&](int e, double v) { pos[e] = v; }, [&](int e, double v) { rot[e] = v; }); \
+        return true;                                                                                \
+    }
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
+RB_HOST_FMA bool link_vel_fma(int n, const double *mdl, const double *ra, const double *q, const double *qd,
+                              double *vel) {
+    switch (n) {
+#define X(N)                                                                                        \
+    case N: {                                                                                       \
+        double a[N], b[N];                                                                          \
+        for (int j = 0; j < N; ++j) {                                                               \
+            a[j] = q[j];                                                                            \
+            b[j] = qd[j];                                                                           \
+        }                                                                                           \
+        dev::link_vel_eval<double, N, false, HostSerialTopo<N>>(mdl, ra, a, b,                      \
+                                                                [&](int e, double v) { vel[e] = v; }); \
+        return true;                                                                                \
+    }
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -319,6 +356,15 @@ bool host_rnea_ext(const Model &m, const double *pk, const double *ra, const dou
 bool host_fd_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                  const double *tau, const double *fext, double *qdd) {
     return host_eval_supported(m) && fd_ext_fma(m.n, pk, ra, q, qd, tau, fext, qdd);
+}
+
+bool host_link_pose(const Model &m, const double *pk, const double *ra, const double *q, double *pos, double *rot) {
+    return host_eval_supported(m) && link_pose_fma(m.n, pk, ra, q, pos, rot);
+}
+
+bool host_link_vel(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                   double *vel) {
+    return host_eval_supported(m) && link_vel_fma(m.n, pk, ra, q, qd, vel);
 }
 
 }  // namespace rbamd

@@ -42,4 +42,11 @@ bool host_rnea_ext(const Model &m, const double *pk, const double *ra, const dou
 bool host_fd_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                  const double *tau, const double *fext, double *qdd);
 
+// Kinematics of every link in its URDF link frame (link_kin_body.hip.hpp): pos [3 n] and rot [9 n]
+// (link j's R_j column-major, x_base = R_j x_link), vel [6 n] (link j's linear, then angular
+// velocity, in its own frame); ra = Model::axis_frames().
+bool host_link_pose(const Model &m, const double *pk, const double *ra, const double *q, double *pos, double *rot);
+bool host_link_vel(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                   double *vel);
+
 }  // namespace rbamd

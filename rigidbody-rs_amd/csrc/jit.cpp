@@ -50,7 +50,7 @@ int jit_nt(JitKind kind) {
     if (kind == JitKind::Rnea || kind == JitKind::RneaExt) return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
     if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt)
         return tuning().fd_nt & 3;
-    const int v = tuning().kin_nt;  // CRBA, fwd_kin, jac
+    const int v = tuning().kin_nt;  // CRBA, fwd_kin, jac, link_pose / link_vel (output-bound, as jac)
     if (v >= 0) return v & 3;
     return kind == JitKind::FwdKin ? 3 : 2;  // 7 rows in / 3 out: non-temporal loads pay too
 }
@@ -325,6 +325,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const bool deriv = kind == JitKind::RneaDeriv || kind == JitKind::FdDeriv;
     const bool vjp = kind == JitKind::RolloutVjp;  // the rollout's adjoint: fd_deriv's scope and link forces
     const bool ext = kind == JitKind::RneaExt || kind == JitKind::FdExt;  // external link wrenches (ext_body.hip.hpp)
+    const bool lk = kind == JitKind::LinkPose || kind == JitKind::LinkVel;  // every link's kinematics (link_kin_body.hip.hpp)
     if ((deriv || vjp) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
@@ -445,8 +446,9 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         }
         o << "};\n";
     }
-    o << (ext                                               ? "#include \"ext_body.hip.hpp\"\n"
-          : vjp                                             ? "#include \"rollout_vjp_body.hip.hpp\"\n"
+    o << (lk                                                ? "#include \"link_kin_body.hip.hpp\"\n"
+          : ext                                             ? "#include \"ext_body.hip.hpp\"\n"
+          : vjp                                            ? "#include \"rollout_vjp_body.hip.hpp\"\n"
           : deriv                                           ? "#include \"rnea_deriv_body.hip.hpp\"\n"
           : kind == JitKind::Rnea                             ? "#include \"rnea_body.hip.hpp\"\n"
           : fdh                                               ? "#include \"fdh_body.hip.hpp\"\n"
@@ -485,7 +487,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         for (size_t k = 0; k < pk.size(); ++k) o << "  " << literal(pk[k], f64) << ",\n";
     }
     o << "};\n";
-    if (ext) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
+    if (ext || lk) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
         const std::vector<double> ra = m.axis_frames();
         o << "static __device__ constexpr T kExtRa[" << ra.size() << "] = {\n";
         for (size_t k = 0; k < ra.size(); ++k) o << "  " << literal(snap(ra[k]), f64) << ",\n";
@@ -608,6 +610,17 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         else
             o << "  rbamd::dev::rnea_ext_lane<T, N, " << F
               << ", Topo>(kModel, kExtRa, q + o, qd + o, qdd + o, fext + o, tau + o, threadIdx.x, ld);\n}\n";
+    } else if (lk) {
+        // one configuration per lane on SoA rows: pos [3 N][ld] and rot [9 N][ld], or vel [6 N][ld]
+        if (kind == JitKind::LinkVel) {
+            sig("const T *__restrict__ q, const T *__restrict__ qd, T *__restrict__ vel, uint32_t B, int64_t ld, int64_t bs");
+            o << lane_prologue << "  rbamd::dev::link_vel_lane<T, N, " << F
+              << ", Topo>(kModel, kExtRa, q + o, qd + o, vel + o, threadIdx.x, ld);\n}\n";
+        } else {
+            sig("const T *__restrict__ q, T *__restrict__ pos, T *__restrict__ rot, uint32_t B, int64_t ld, int64_t bs");
+            o << lane_prologue << "  rbamd::dev::link_pose_lane<T, N, " << F
+              << ", Topo>(kModel, kExtRa, q + o, pos + o, rot + o, threadIdx.x, ld);\n}\n";
+        }
     } else if (deriv) {
         // one configuration per lane on SoA rows; a NULL output is neither evaluated nor stored
         const bool fd = kind == JitKind::FdDeriv;

@@ -36,11 +36,14 @@ namespace rbamd {
 // RneaExt / FdExt: inverse / forward dynamics under external link wrenches (ext_body.hip.hpp), every
 // model, hipRTC only, one configuration per lane on SoA rows; FdExt takes the formulation
 // jit_fd_form picks for Fd.  Internal too: multibody_ext_jit_source / _compile.
+// LinkPose / LinkVel: pose / spatial velocity of every link in its URDF link frame
+// (link_kin_body.hip.hpp), every model, hipRTC only, one configuration per lane on SoA rows.
+// Internal too: multibody_link_kin_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
-    RolloutVjp = 9, RneaExt = 10, FdExt = 11
+    RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13
 };
-constexpr int kJitKinds = 12;
+constexpr int kJitKinds = 14;
 constexpr int kJitPublicKinds = 9;
 
 // Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds and the

@@ -101,14 +101,20 @@ _SIGNATURES = {
     "multibody_fd_ext": (_int, [_vp] + [_dp] * 5),
     "multibody_ext_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
     "multibody_ext_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
+    # kinematics of every link: one configuration (handle, q, pos, rot) / (handle, q, qd, vel);
+    # inspection (handle, vel, f64, batch, ...)
+    "multibody_link_pose": (_int, [_vp] + [_dp] * 3),
+    "multibody_link_vel": (_int, [_vp] + [_dp] * 3),
+    "multibody_link_kin_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
+    "multibody_link_kin_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
 }
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
 _ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7,
-           "rnea_ext": 5, "fd_ext": 5}
+           "rnea_ext": 5, "fd_ext": 5, "link_pose": 3, "link_vel": 3}
 for _t in ("f32", "f64"):
     for _k, _n in _ARRAYS.items():
         _SIGNATURES[f"multibody_{_k}_batch_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _i64, _vp])
-        if not _k.endswith(("_deriv", "_ext")):
+        if not _k.endswith(("_deriv", "_ext")) and not _k.startswith("link_"):
             _SIGNATURES[f"multibody_{_k}_batch_tiled_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _vp])
         if _k not in ("crba", "fwd_kin", "jac"):
             _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
@@ -515,6 +521,90 @@ class Multibody:
     def fd_ext_batch_host(self, q, qd, tau, fext, dtype=np.float64):
         """Blocking host form of fd_ext_batch on numpy arrays."""
         return self._ext_host("fd_ext", q, qd, tau, fext, dtype)
+
+    # ---- kinematics of every link, in its own URDF link frame (the frame fext is given in)
+    def link_pose(self, q):
+        """multibody_link_pose: (pos [n, 3], rot [n, 3, 3]) of one configuration, on the calling thread:
+        link j's frame origin in the base frame and its rotation R_j, x_base = R_j x_link."""
+        q = _dvec(q, self.n)
+        pos, rot = np.empty(3 * self.n), np.empty(9 * self.n)
+        _check(_lib.multibody_link_pose(self._h, *[a.ctypes.data_as(_dp) for a in (q, pos, rot)]), "link_pose")
+        return pos.reshape(self.n, 3), rot.reshape(self.n, 3, 3).transpose(0, 2, 1)  # column-major per link
+
+    def link_vel(self, q, qd):
+        """multibody_link_vel: vel [n, 6] of one configuration: link j's linear, then angular velocity,
+        in its own frame (vel_j = J_j(q) qd)."""
+        q, qd = _dvec(q, self.n), _dvec(qd, self.n)
+        vel = np.empty(6 * self.n)
+        _check(_lib.multibody_link_vel(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, vel)]), "link_vel")
+        return vel.reshape(self.n, 6)
+
+    def link_kin_jit_source(self, vel=False, f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the link_pose (vel=False) / link_vel (vel=True) kernel
+        (multibody_link_kin_jit_source)."""
+        a = (self._h, int(bool(vel)), int(bool(f64)), int(batch))
+        n = _lib.multibody_link_kin_jit_source(*a, None, 0)
+        if n < 0:
+            raise RigidBodyError(last_error())
+        buf = ctypes.create_string_buffer(n + 1)
+        _lib.multibody_link_kin_jit_source(*a, buf, n + 1)
+        return buf.value.decode()
+
+    def link_kin_jit_compile(self, vel=False, f64=False, arch="gfx950", batch=1 << 20) -> int:
+        r = _lib.multibody_link_kin_jit_compile(self._h, int(bool(vel)), int(bool(f64)), int(batch), arch.encode())
+        if r < 0:
+            raise RigidBodyError(last_error())
+        return r
+
+    def _link_kin_call(self, kind, ins, outs, stream):
+        """ins: (tensor, name) pairs of [n, B] inputs; outs: (tensor or None, name, rows per link)."""
+        q = _soa(ins[0][0], self.n, ins[0][1])
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        live = [q] + [_soa(t, self.n, name, q.dtype, B) for t, name in ins[1:]]
+        res = []
+        for t, name, rows in outs:
+            if t is None:
+                t = torch.empty((rows * self.n, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
+            else:
+                _soa(t, rows * self.n, name, q.dtype, B)
+            res.append(t)
+        live += res
+        ld = _same_ld(live)
+        dev = _one_device(live)
+        fn = getattr(_lib, f"multibody_{kind}_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, *[t.data_ptr() for t in live], B, ld, _stream_ptr(stream, dev)), f"{kind}_batch")
+        return res
+
+    def link_pose_batch(self, q, pos=None, rot=None, stream=None):
+        """multibody_link_pose_batch_*: q [n, B] -> (pos [3 n, B], rot [9 n, B]); row 3 j + c of pos is
+        component c of link j's frame origin in the base frame, row 9 j + row + 3 col of rot the
+        rotation R_j (x_base = R_j x_link)."""
+        pos, rot = self._link_kin_call("link_pose", [(q, "q")], [(pos, "pos", 3), (rot, "rot", 9)], stream)
+        return pos, rot
+
+    def link_vel_batch(self, q, qd, out=None, stream=None):
+        """multibody_link_vel_batch_*: q, qd [n, B] -> vel [6 n, B]; rows 6 j + 0..2 the linear, 6 j +
+        3..5 the angular velocity of link j, in its own URDF link frame (the rows of fext)."""
+        return self._link_kin_call("link_vel", [(q, "q"), (qd, "qd")], [(out, "vel", 6)], stream)[0]
+
+    def _link_kin_host(self, kind, ins, rows, dtype):
+        arrs = _host_soa(ins, self.n, dtype)
+        B = arrs[0].shape[1]
+        outs = [np.empty((r * self.n, B), dtype=arrs[0].dtype) for r in rows]
+        fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in (*arrs, *outs)], B), f"{kind}_batch_host")
+        return outs
+
+    def link_pose_batch_host(self, q, dtype=np.float64):
+        """Blocking host form of link_pose_batch on numpy arrays -> (pos, rot)."""
+        return tuple(self._link_kin_host("link_pose", (q,), (3, 9), dtype))
+
+    def link_vel_batch_host(self, q, qd, dtype=np.float64):
+        """Blocking host form of link_vel_batch on numpy arrays."""
+        return self._link_kin_host("link_vel", (q, qd), (6,), dtype)[0]
 
     # ------------------------------------------------------- batched, device [n, B]
     def _soa_call(self, kind, ins, outs, stream):
