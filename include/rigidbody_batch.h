@@ -587,6 +587,128 @@ int multibody_link_vel(const Multibody *mb, const double *q, const double *qd, d
 int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_link_kin_jit_compile(const Multibody *mb, int vel, int f64, int64_t batch, const char *arch);
 
+/* ---- compliant ground contact ---------------------------------------------------- */
+/* The step between the link kinematics and the external wrenches: a contact model that maps
+ * (q, qd) to fext, and a fused K-step rollout that evaluates it on chip at every step and
+ * integrates fd_ext under it (one launch; a step moves the step's tau and its traj row through
+ * memory and nothing else).
+ *
+ * A contact set belongs to a model.  It holds P points, 1 <= P <= RB_CONTACT_MAX_POINTS, each with a
+ * moving-link index l_p in 0 .. n-1 (the numbering of multibody_topology; the six virtual links of a
+ * floating base count like any other) and a position c_p in that link's URDF link frame; one plane
+ * in the base frame, a unit normal nhat and an offset d, the free side nhat . x > d; and four law
+ * parameters: stiffness k >= 0 [N/m], damping c >= 0 [s/m], friction mu >= 0, slip velocity
+ * v_s > 0 [m/s].  Several points may sit on one link.
+ *
+ * The law.  For a state (q, v), with pos_j, R_j, vel_j = [lin_j; ang_j] exactly as
+ * multibody_link_pose / multibody_link_vel define them:
+ *
+ *   x_p   = pos_l + R_l c_p                          point in the base frame
+ *   xd_p  = R_l (lin_l + ang_l x c_p)                its velocity in the base frame
+ *   phi   = max(d - nhat . x_p, 0)                   penetration depth
+ *   phid  = -nhat . xd_p                             penetration rate
+ *   f_n   = max(k * phi * (1 + c * phid), 0)         Hunt-Crossley normal force, never adhesive
+ *   v_t   = xd_p + phid * nhat                       tangential velocity
+ *   F_p   = f_n * nhat - mu * f_n * v_t / sqrt(v_t . v_t + v_s^2)
+ *   g_p   = R_l^T F_p                                the force in the link frame
+ *   fext_l += [ g_p ; c_p x g_p ]                    [force; moment], the ABI's fext row order
+ *
+ * Every piece is continuous in the state: the normal force goes to zero with the depth, the
+ * friction is regularised by v_s.  Rows of links with no point are exact zeros.
+ *
+ * The fused rollout does, at step k:
+ *
+ *   fext     = contact(q_k, v_k)
+ *   a_k      = fd_ext(q_k, v_k, tau_k, fext)
+ *   v_{k+1}  = v_k + dt a_k
+ *   q_{k+1}  = q_k + dt v_{k+1}
+ *   traj[k]  = q_{k+1}
+ *
+ * -- multibody_rollout_batch's integrator and fused-multiply-add order.  It is an explicit penalty
+ * method: stability needs roughly dt * sqrt(k / m_link) < 1, which is the caller's responsibility.
+ *
+ * The set rides on the handle: multibody_with_contacts returns a NEW immutable handle, the same
+ * model plus the set (mb is not modified; free both).  The set is model data and is compiled into
+ * the kernels like the rest of the model, so a link without a point costs nothing and mu == 0 drops
+ * the friction -- and changing a stiffness is a different model that compiles its own kernels.
+ * multibody_export_blob / multibody_new_from_blob carry the set; the blob of a model without one is
+ * what it was.  multibody_with_contacts returns NULL (rb_last_error names the field) for n_points
+ * outside 1..16, a link index outside 0..n-1, any non-finite value, | |normal| - 1 | > 1e-6, a
+ * negative stiffness, damping or friction, slip_velocity <= 0.
+ *
+ * Layout: q, qd [n][ld]; fext [6 n][ld] as multibody_rnea_ext takes it; cforce [3 P][ld], F_p in the
+ * base frame at row 3 p + c; tau_seq, traj [K n][ld] as multibody_rollout_batch; q and qd of the
+ * rollout are overwritten with the final state.  Every array is required, traj and cforce included.
+ *
+ * Checks, in order: handle (RB_ERR_NULL), batch >= 0, ld >= batch (RB_ERR_ARG), the rollout's K < 0
+ * (RB_ERR_ARG "negative step count"), batch == 0 or the rollout's K == 0 (RB_OK, nothing else looked
+ * at), a NULL array (RB_ERR_NULL), an output -- the rollout's q and qd included -- that is also an
+ * input or another output (RB_ERR_ARG), a model without a contact set (RB_ERR_UNSUPPORTED, naming
+ * multibody_with_contacts), then hipRTC.
+ *
+ * Scope: every model the external-wrench kernels run.  Model-specialised (hipRTC) kernels only, one
+ * configuration per lane, SoA rows, no kind number, batches split at 2^28.  The rollout's forward
+ * dynamics is the formulation multibody_rollout_batch takes for the model.
+ *
+ * Input domain: as above; a configuration with a NaN / Inf input or an angle past the bound gets NaN
+ * in every output, the others are unaffected.  The rollout checks the state and tau_k at every
+ * step: everything from the first bad step on is NaN.
+ *
+ * Accuracy (tests/test_contact_host.py, tests/test_gpu_contact.py; reference tests/contact_ref.py,
+ * the law above on tests/link_kin_ref.py and the oracle's forward dynamics).  fp64: fext, cforce
+ * |d| <= 1e-9 (1 + |ref|); traj and the final state 1e-7 (1 + |ref|), against the reference and
+ * against the composed contact_wrench / fd_ext / update sequence; the power identity
+ * sum_p F_p . xd_p = sum_j fext_j . vel_j to 1e-8 scaled.  fp32 against the fp64 kernel on the same
+ * fp32-rounded inputs, per configuration and array: contact_wrench max|d| <= 1e-4 (1 + max|ref|);
+ * rollout_contact (K = 4, dt = 1e-3) traj and final state 4e-4 (1 + max|ref|) -- 8x the measured
+ * maximum, 4.7e-5 (the 16-link chain's final qd).  Measured (MI355X, B = 257, about half the points
+ * in contact): fp64 wrench 6.2e-13 at most; fused rollout against the composition 2.8e-14, against
+ * the reference 1.3e-13; fp32 wrench 1.7e-5 FR3 / 7.1e-5 16 links / 1.0e-5 at most the others; fp32
+ * rollout traj 6.4e-6 at most, final qd 4.7e-5 at most.  Single-configuration forms on the host:
+ * wrench 1.4e-12 at most (30 links), rollout (K = 3) 1.4e-11. */
+enum { RB_CONTACT_MAX_POINTS = 16 };
+typedef struct {
+    int n_points;
+    int link[RB_CONTACT_MAX_POINTS];
+    double point[RB_CONTACT_MAX_POINTS][3];
+    double normal[3];
+    double offset;
+    double stiffness, damping, friction, slip_velocity;
+} rb_contact_model;
+
+/* A NEW immutable handle: the same model plus the contact set.  mb is not modified. */
+Multibody *multibody_with_contacts(const Multibody *mb, const rb_contact_model *cm);
+/* Returns n_points (0: the model carries no contact set); fills *out when non-NULL. */
+int multibody_contact_model(const Multibody *mb, rb_contact_model *out);
+
+int multibody_contact_wrench_batch_f32(const Multibody *mb, const float *q, const float *qd, float *fext,
+                                       float *cforce, int64_t batch, int64_t ld, void *stream);
+int multibody_contact_wrench_batch_f64(const Multibody *mb, const double *q, const double *qd, double *fext,
+                                       double *cforce, int64_t batch, int64_t ld, void *stream);
+int multibody_rollout_contact_batch_f32(const Multibody *mb, float *q, float *qd, const float *tau_seq, double dt,
+                                        int K, float *traj, int64_t batch, int64_t ld, void *stream);
+int multibody_rollout_contact_batch_f64(const Multibody *mb, double *q, double *qd, const double *tau_seq, double dt,
+                                        int K, double *traj, int64_t batch, int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch). */
+int multibody_contact_wrench_batch_host_f32(const Multibody *mb, const float *q, const float *qd, float *fext,
+                                            float *cforce, int64_t batch);
+int multibody_contact_wrench_batch_host_f64(const Multibody *mb, const double *q, const double *qd, double *fext,
+                                            double *cforce, int64_t batch);
+int multibody_rollout_contact_batch_host_f32(const Multibody *mb, float *q, float *qd, const float *tau_seq, double dt,
+                                             int K, float *traj, int64_t batch);
+int multibody_rollout_contact_batch_host_f64(const Multibody *mb, double *q, double *qd, const double *tau_seq,
+                                             double dt, int K, double *traj, int64_t batch);
+/* One configuration, fp64, on the calling thread: the scope of multibody_rnea_ext (serial revolute
+ * chains of a multibody_supported_dofs length on an FMA3 / AVX2 CPU). */
+int multibody_contact_wrench(const Multibody *mb, const double *q, const double *qd, double *fext, double *cforce);
+int multibody_rollout_contact(const Multibody *mb, double *q, double *qd, const double *tau_seq, double dt, int K,
+                              double *traj);
+/* Inspection of those kernels (no kind number): rollout != 0 selects rollout_contact, else
+ * contact_wrench; a model without a contact set has the empty source / -RB_ERR_UNSUPPORTED;
+ * otherwise as multibody_ext_jit_source / _compile. */
+int multibody_contact_jit_source(const Multibody *mb, int rollout, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_contact_jit_compile(const Multibody *mb, int rollout, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

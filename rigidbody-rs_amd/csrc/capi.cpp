@@ -318,6 +318,25 @@ hipError_t launch_link_vel(const Multibody *mb, const T *q, const T *qd, T *vel,
                       [&] { return no_generic(mb, "the link kinematics run"); });
 }
 
+// Compliant ground contact (contact_body.hip.hpp): model-specialised kernels only, SoA rows, every
+// model that carries a contact set; fext has 6 n rows, cforce 3 P.
+template <typename T>
+hipError_t launch_contact_wrench(const Multibody *mb, const T *q, const T *qd, T *fext, T *cforce, uint32_t B,
+                                 int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    void *args[] = {&q, &qd, &fext, &cforce, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::ContactWrench, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the contact kernels run"); });
+}
+
+template <typename T>
+hipError_t launch_rollout_contact(const Multibody *mb, T *q, T *qd, const T *tau_seq, T dt, int K, T *traj, uint32_t B,
+                                  int64_t ld, hipStream_t s) {
+    void *args[] = {&q, &qd, &tau_seq, &dt, &K, &traj, &B, &ld};
+    return launch_any(mb, rbamd::JitKind::RolloutContact, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the contact kernels run"); });
+}
+
 constexpr int64_t kChunk = int64_t(1) << 28;  // per-launch batch cap: b * sizeof(T) < 2^32
 
 int check_batch(const Multibody *mb, int64_t batch, int64_t ld) {
@@ -623,6 +642,53 @@ int link_vel_batch(const Multibody *mb, const T *q, const T *qd, T *vel, int64_t
     });
 }
 
+// The contact entry points' own argument checks: every array present, no output (the rollout's
+// state included) that is also an input or another output, a model that carries a contact set.
+template <typename T>
+int contact_args_ok(const Multibody *mb, bool rollout, std::initializer_list<const T *> in,
+                    std::initializer_list<const T *> out) {
+    for (const T *p : in)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    for (const T *p : out)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    return deriv_args_ok<T>(mb, rollout ? rbamd::JitKind::RolloutContact : rbamd::JitKind::ContactWrench,
+                            rollout ? "rollout_contact" : "contact_wrench", in, out);
+}
+
+// The rollouts' step count, after handle / batch / ld and before the empty-batch return; *done: K == 0.
+int rollout_steps(const Multibody *mb, int64_t batch, int64_t ld, int K, bool *done) {
+    *done = false;
+    if (int rc = check_batch(mb, batch, ld)) return rc;
+    if (K < 0) return set_err(RB_ERR_ARG, "negative step count");
+    *done = K == 0;
+    return RB_OK;
+}
+
+template <typename T>
+int contact_wrench_batch(const Multibody *mb, const T *q, const T *qd, T *fext, T *cforce, int64_t batch, int64_t ld,
+                         void *stream) {
+    auto args_ok = [&] { return contact_args_ok<T>(mb, false, {q, qd}, {fext, cforce}); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "contact_wrench launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n, np = mb->model.contacts.n_points;
+        return launch_contact_wrench<T>(mb, at(q, n), at(qd, n), at(fext, 6 * n), at(cforce, 3 * np), nb, ld,
+                                        (hipStream_t)stream);
+    });
+}
+
+template <typename T>
+int rollout_contact_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt, int K, T *traj, int64_t batch,
+                          int64_t ld, void *stream) {
+    bool done = false;
+    if (int rc = rollout_steps(mb, batch, ld, K, &done)) return rc;
+    if (done) return RB_OK;
+    auto args_ok = [&] { return contact_args_ok<T>(mb, true, {tau_seq}, {q, qd, traj}); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "rollout_contact launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;  // tau_seq and traj: K * n rows
+        return launch_rollout_contact<T>(mb, at(q, n), at(qd, n), at(tau_seq, K * n), (T)dt, K, at(traj, K * n), nb, ld,
+                                         (hipStream_t)stream);
+    });
+}
+
 template <typename T>
 int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt, int K, T *traj, int64_t batch,
                   int64_t ld, void *stream) {
@@ -844,6 +910,35 @@ int link_vel_host(const Multibody *mb, const T *q, const T *qd, T *vel, int64_t 
 }
 
 template <typename T>
+int contact_wrench_host(const Multibody *mb, const T *q, const T *qd, T *fext, T *cforce, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0, np = mb ? mb->model.contacts.n_points : 0;
+    return host_call_rows<T, 2, 2>(
+        mb, {q, qd}, {n, n}, {fext, cforce}, {6 * n, 3 * np}, 0, false, batch,
+        [&] { return contact_args_ok<T>(mb, false, {q, qd}, {fext, cforce}); },
+        [&](T **i, T **o, hipStream_t s) { return contact_wrench_batch<T>(mb, i[0], i[1], o[0], o[1], batch, batch, s); });
+}
+
+// q and qd are read and written: their device copies go back to the host after the launch.
+template <typename T>
+int rollout_contact_host(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt, int K, T *traj, int64_t batch) {
+    bool done = false;
+    if (int rc = rollout_steps(mb, batch, batch, K, &done)) return rc;
+    if (done) return RB_OK;
+    const int64_t n = mb->model.n, kn = (int64_t)K * n;
+    return host_call_rows<T, 3, 1>(
+        mb, {q, qd, tau_seq}, {n, n, kn}, {traj}, {kn}, 0, false, batch,
+        [&] { return contact_args_ok<T>(mb, true, {tau_seq}, {q, qd, traj}); },
+        [&](T **i, T **o, hipStream_t s) {
+            int rc = rollout_contact_batch<T>(mb, i[0], i[1], i[2], dt, K, o[0], batch, batch, s);
+            const size_t bytes = (size_t)n * (size_t)batch * sizeof(T);
+            hipError_t e = hipSuccess;
+            if (rc == RB_OK) e = hipMemcpyAsync(q, i[0], bytes, hipMemcpyDeviceToHost, s);
+            if (rc == RB_OK && e == hipSuccess) e = hipMemcpyAsync(qd, i[1], bytes, hipMemcpyDeviceToHost, s);
+            return e == hipSuccess ? rc : hip_err(e, "hipMemcpyAsync D2H");
+        });
+}
+
+template <typename T>
 int rollout_vjp_host(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
                      const T *gqd, T *g_q0, T *g_qd0, T *g_tau, int64_t batch) {
     // the step count comes before the arrays, as in the device form
@@ -968,7 +1063,7 @@ unsigned multibody_flags(const Multibody *mb) {
 
 int64_t multibody_blob_size(const Multibody *mb) {
     if (!mb) return -set_err(RB_ERR_NULL, "NULL Multibody handle");
-    return rbamd::kBlobHeader + (int64_t)mb->model.n * rbamd::kBlobPerLink;
+    return rbamd::kBlobHeader + (int64_t)mb->model.n * rbamd::kBlobPerLink + mb->model.contacts.blob_size();
 }
 
 int multibody_export_blob(const Multibody *mb, double *out, int64_t len) {
@@ -986,6 +1081,49 @@ Multibody *multibody_new_from_blob(const double *blob, int64_t len) {
         set_err(RB_ERR_ARG, ex.what());
         return nullptr;
     }
+}
+
+Multibody *multibody_with_contacts(const Multibody *mb, const rb_contact_model *cm) {
+    if (!mb) { set_err(RB_ERR_NULL, "NULL Multibody handle"); return nullptr; }
+    if (!cm) { set_err(RB_ERR_NULL, "NULL contact model"); return nullptr; }
+    rbamd::ContactSet c;
+    c.n_points = cm->n_points;
+    if (c.n_points >= 1 && c.n_points <= rbamd::kContactMaxPoints)
+        for (int p = 0; p < c.n_points; ++p) {
+            c.link[p] = cm->link[p];
+            for (int k = 0; k < 3; ++k) c.point[p][k] = cm->point[p][k];
+        }
+    for (int k = 0; k < 3; ++k) c.normal[k] = cm->normal[k];
+    c.offset = cm->offset;
+    c.stiffness = cm->stiffness;
+    c.damping = cm->damping;
+    c.friction = cm->friction;
+    c.slip_velocity = cm->slip_velocity;
+    const std::string why = c.refusal(mb->model.n);
+    if (!why.empty()) { set_err(RB_ERR_ARG, why); return nullptr; }
+    rbamd::Model m = mb->model;
+    m.contacts = c;
+    return make(std::move(m));
+}
+
+int multibody_contact_model(const Multibody *mb, rb_contact_model *out) {
+    if (!mb) return -set_err(RB_ERR_NULL, "NULL Multibody handle");
+    const rbamd::ContactSet &c = mb->model.contacts;
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->n_points = c.n_points;
+        for (int p = 0; p < c.n_points; ++p) {
+            out->link[p] = c.link[p];
+            for (int k = 0; k < 3; ++k) out->point[p][k] = c.point[p][k];
+        }
+        for (int k = 0; k < 3; ++k) out->normal[k] = c.normal[k];
+        out->offset = c.offset;
+        out->stiffness = c.stiffness;
+        out->damping = c.damping;
+        out->friction = c.friction;
+        out->slip_velocity = c.slip_velocity;
+    }
+    return c.n_points;
 }
 
 int multibody_dof(const Multibody *mb) { return mb ? mb->model.n : -set_err(RB_ERR_NULL, "NULL Multibody handle"); }
@@ -1093,6 +1231,16 @@ int ext_kind(int fd) { return (int)(fd ? rbamd::JitKind::FdExt : rbamd::JitKind:
 // ... nor the link-kinematics kernels (check_ext_query's checks): vel selects link_vel (else link_pose).
 int link_kin_kind(int vel) { return (int)(vel ? rbamd::JitKind::LinkVel : rbamd::JitKind::LinkPose); }
 
+// ... nor the contact kernels: rollout selects rollout_contact (else contact_wrench); a model without
+// a contact set has neither (RB_ERR_UNSUPPORTED, the empty source).
+int contact_kind(int rollout) {
+    return (int)(rollout ? rbamd::JitKind::RolloutContact : rbamd::JitKind::ContactWrench);
+}
+int check_contact_query(const Multibody *mb, int rollout, int64_t batch) {
+    if (int rc = check_ext_query(mb, batch)) return rc;
+    return deriv_supported(mb, (rbamd::JitKind)contact_kind(rollout));
+}
+
 void note_jit_errors(const Multibody *mb) {
     for (std::string &err : mb->cache.jit_errors()) g_last_error = std::move(err);
 }
@@ -1166,6 +1314,15 @@ int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t
 int64_t multibody_link_kin_jit_compile(const Multibody *mb, int vel, int f64, int64_t batch, const char *arch) {
     if (int rc = check_ext_query(mb, batch)) return -rc;
     return compile_query(mb, link_kin_kind(vel), f64, batch, 0, arch);
+}
+
+int multibody_contact_jit_source(const Multibody *mb, int rollout, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_contact_query(mb, rollout, batch), contact_kind(rollout), f64, batch, 0, buf, cap);
+}
+
+int64_t multibody_contact_jit_compile(const Multibody *mb, int rollout, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_contact_query(mb, rollout, batch)) return -rc;
+    return compile_query(mb, contact_kind(rollout), f64, batch, 0, arch);
 }
 
 int multibody_upload(const Multibody *mb) {
@@ -1542,6 +1699,72 @@ int multibody_link_pose(const Multibody *mb, const double *q, double *pos, doubl
 }
 int multibody_link_vel(const Multibody *mb, const double *q, const double *qd, double *vel) {
     return link_kin_single(mb, true, q, qd, vel, nullptr);
+}
+
+// ------------------------------------------------------------- compliant ground contact
+int multibody_contact_wrench_batch_f32(const Multibody *mb, const float *q, const float *qd, float *fext,
+                                       float *cforce, int64_t batch, int64_t ld, void *stream) {
+    return contact_wrench_batch<float>(mb, q, qd, fext, cforce, batch, ld, stream);
+}
+int multibody_contact_wrench_batch_f64(const Multibody *mb, const double *q, const double *qd, double *fext,
+                                       double *cforce, int64_t batch, int64_t ld, void *stream) {
+    return contact_wrench_batch<double>(mb, q, qd, fext, cforce, batch, ld, stream);
+}
+int multibody_contact_wrench_batch_host_f32(const Multibody *mb, const float *q, const float *qd, float *fext,
+                                            float *cforce, int64_t batch) {
+    return contact_wrench_host<float>(mb, q, qd, fext, cforce, batch);
+}
+int multibody_contact_wrench_batch_host_f64(const Multibody *mb, const double *q, const double *qd, double *fext,
+                                            double *cforce, int64_t batch) {
+    return contact_wrench_host<double>(mb, q, qd, fext, cforce, batch);
+}
+int multibody_rollout_contact_batch_f32(const Multibody *mb, float *q, float *qd, const float *tau_seq, double dt,
+                                        int K, float *traj, int64_t batch, int64_t ld, void *stream) {
+    return rollout_contact_batch<float>(mb, q, qd, tau_seq, dt, K, traj, batch, ld, stream);
+}
+int multibody_rollout_contact_batch_f64(const Multibody *mb, double *q, double *qd, const double *tau_seq, double dt,
+                                        int K, double *traj, int64_t batch, int64_t ld, void *stream) {
+    return rollout_contact_batch<double>(mb, q, qd, tau_seq, dt, K, traj, batch, ld, stream);
+}
+int multibody_rollout_contact_batch_host_f32(const Multibody *mb, float *q, float *qd, const float *tau_seq, double dt,
+                                             int K, float *traj, int64_t batch) {
+    return rollout_contact_host<float>(mb, q, qd, tau_seq, dt, K, traj, batch);
+}
+int multibody_rollout_contact_batch_host_f64(const Multibody *mb, double *q, double *qd, const double *tau_seq,
+                                             double dt, int K, double *traj, int64_t batch) {
+    return rollout_contact_host<double>(mb, q, qd, tau_seq, dt, K, traj, batch);
+}
+
+// Single configuration, fp64, on the calling thread (host_eval.cpp): multibody_rnea_ext's scope.
+static int contact_single_scope(const Multibody *mb, const char *op) {
+    if (!mb->model.serial_revolute())
+        return set_err(RB_ERR_UNSUPPORTED, std::string(op) + ": the single-configuration form evaluates serial revolute "
+                                           "chains only (kinematic trees, prismatic joints and a floating base take "
+                                           "the batched entry points)");
+    return RB_OK;
+}
+static int contact_single_no_fma(const char *op) {
+    return set_err(RB_ERR_UNSUPPORTED, std::string(op) + ": the single-configuration form runs on the host and needs "
+                                       "an FMA3 / AVX2 CPU");
+}
+int multibody_contact_wrench(const Multibody *mb, const double *q, const double *qd, double *fext, double *cforce) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = contact_args_ok<double>(mb, false, {q, qd}, {fext, cforce})) return rc;
+    if (int rc = contact_single_scope(mb, "contact_wrench")) return rc;
+    if (!rbamd::host_contact_wrench(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, fext, cforce))
+        return contact_single_no_fma("contact_wrench");
+    return RB_OK;
+}
+int multibody_rollout_contact(const Multibody *mb, double *q, double *qd, const double *tau_seq, double dt, int K,
+                              double *traj) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (K < 0) return set_err(RB_ERR_ARG, "negative step count");
+    if (K == 0) return RB_OK;
+    if (int rc = contact_args_ok<double>(mb, true, {tau_seq}, {q, qd, traj})) return rc;
+    if (int rc = contact_single_scope(mb, "rollout_contact")) return rc;
+    if (!rbamd::host_rollout_contact(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, tau_seq, dt, K, traj))
+        return contact_single_no_fma("rollout_contact");
+    return RB_OK;
 }
 
 // ------------------------------------------------------------- batched (host)

@@ -18,6 +18,7 @@
 #include "rollout_vjp_body.hip.hpp"  // first: rnea_deriv_body declares the host reciprocal fdh_body's L D L^T takes
 #include "crba_body.hip.hpp"
 #include "dofs.hpp"
+#include "contact_body.hip.hpp"
 #include "ext_body.hip.hpp"
 #include "kernels.hpp"
 #include "link_kin_body.hip.hpp"
@@ -304,6 +305,85 @@ RB_HOST_FMA bool link_vel_fma(int n, const double *mdl, const double *ra, const 
     }
 }
 
+// The model's contact set as contact_body's `Con`: run-time values, a slot per point at most.
+template <int N>
+struct HostCon {
+    static constexpr int kSlots = kContactMaxPoints;
+    const ContactSet &c;
+    int slot[N];
+    explicit HostCon(const ContactSet &set) : c(set) {
+        int slots = 0;
+        for (int j = 0; j < N; ++j) {
+            slot[j] = -1;
+            for (int p = 0; p < c.n_points && slot[j] < 0; ++p)
+                if (c.link[p] == j) slot[j] = slots++;
+        }
+    }
+    int points() const { return c.n_points; }
+    int link(int p) const { return c.link[p]; }
+    int slot_of(int j) const { return slot[j]; }
+    double point(int p, int k) const { return c.point[p][k]; }
+    double normal(int k) const { return c.normal[k]; }
+    double offset() const { return c.offset; }
+    double stiffness() const { return c.stiffness; }
+    double damping() const { return c.damping; }
+    double friction() const { return c.friction; }
+    double slip_velocity() const { return c.slip_velocity; }
+};
+
+RB_HOST_FMA bool contact_wrench_fma(int n, const ContactSet &cs, const double *mdl, const double *ra, const double *q,
+                                    const double *qd, double *fext, double *cforce) {
+    switch (n) {
+#define X(N)                                                                                        \
+    case N: {                                                                                       \
+        double a[N], b[N];                                                                          \
+        for (int j = 0; j < N; ++j) {                                                               \
+            a[j] = q[j];                                                                            \
+            b[j] = qd[j];                                                                           \
+        }                                                                                           \
+        dev::contact_wrench_eval<double, N, false, HostSerialTopo<N>>(                              \
+            mdl, ra, HostCon<N>(cs), a, b, [&](int e, double v) { fext[e] = v; },                   \
+            [&](int e, double v) { cforce[e] = v; });                                               \
+        return true;                                                                                \
+    }
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
+template <int N>
+RB_HOST_FMA bool rollout_contact_fma_n(const ContactSet &cs, const double *mdl, const double *ra, double *q, double *qd,
+                                       const double *tau_seq, double dt, int K, double *traj) {
+    double a[N], b[N];
+    for (int j = 0; j < N; ++j) {
+        a[j] = q[j];
+        b[j] = qd[j];
+    }
+    dev::rollout_contact_steps<double, N, false, HostSerialTopo<N>, (N <= kHostFdDerivMaxLinks)>(
+        mdl, ra, HostCon<N>(cs), a, b, dt, K,
+        [&](int k, double(&tv)[N]) {
+            for (int j = 0; j < N; ++j) tv[j] = tau_seq[(size_t)k * N + j];
+        },
+        [&](int k, int j, double v) { traj[(size_t)k * N + j] = v; });
+    for (int j = 0; j < N; ++j) {
+        q[j] = a[j];
+        qd[j] = b[j];
+    }
+    return true;
+}
+
+RB_HOST_FMA bool rollout_contact_fma(int n, const ContactSet &cs, const double *mdl, const double *ra, double *q,
+                                     double *qd, const double *tau_seq, double dt, int K, double *traj) {
+    switch (n) {
+#define X(N) \
+    case N: return rollout_contact_fma_n<N>(cs, mdl, ra, q, qd, tau_seq, dt, K, traj);
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -365,6 +445,18 @@ bool host_link_pose(const Model &m, const double *pk, const double *ra, const do
 bool host_link_vel(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                    double *vel) {
     return host_eval_supported(m) && link_vel_fma(m.n, pk, ra, q, qd, vel);
+}
+
+bool host_contact_wrench(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                         double *fext, double *cforce) {
+    return host_eval_supported(m) && m.contacts.n_points > 0 &&
+           contact_wrench_fma(m.n, m.contacts, pk, ra, q, qd, fext, cforce);
+}
+
+bool host_rollout_contact(const Model &m, const double *pk, const double *ra, double *q, double *qd,
+                          const double *tau_seq, double dt, int K, double *traj) {
+    return host_eval_supported(m) && m.contacts.n_points > 0 &&
+           rollout_contact_fma(m.n, m.contacts, pk, ra, q, qd, tau_seq, dt, K, traj);
 }
 
 }  // namespace rbamd

@@ -49,4 +49,12 @@ bool host_link_pose(const Model &m, const double *pk, const double *ra, const do
 bool host_link_vel(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                    double *vel);
 
+// Compliant ground contact (contact_body.hip.hpp) of a model that carries a contact set: fext [6 n]
+// and cforce [3 P] of one configuration; K steps of the fused rollout (q, qd overwritten with the
+// final state, traj [K n]) on the forward-dynamics form host_fd_ext takes.
+bool host_contact_wrench(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                         double *fext, double *cforce);
+bool host_rollout_contact(const Model &m, const double *pk, const double *ra, double *q, double *qd,
+                          const double *tau_seq, double dt, int K, double *traj);
+
 }  // namespace rbamd

@@ -48,9 +48,11 @@ std::string literal(double x, bool f64) {
 int jit_nt(JitKind kind) {
     // (the external-wrench kinds follow their plain neighbours: every row is touched once)
     if (kind == JitKind::Rnea || kind == JitKind::RneaExt) return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
-    if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt)
+    if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt ||
+        kind == JitKind::RolloutContact)
         return tuning().fd_nt & 3;
-    const int v = tuning().kin_nt;  // CRBA, fwd_kin, jac, link_pose / link_vel (output-bound, as jac)
+    // CRBA, fwd_kin, jac, link_pose / link_vel and contact_wrench (output-bound, as jac)
+    const int v = tuning().kin_nt;
     if (v >= 0) return v & 3;
     return kind == JitKind::FwdKin ? 3 : 2;  // 7 rows in / 3 out: non-temporal loads pay too
 }
@@ -144,6 +146,9 @@ int fd_form(const ModelShape &m, JitKind kind) {
 int jit_fd_form(const Model &m, JitKind kind) { return fd_form({m.n, m.serial_revolute()}, kind); }
 
 std::string jit_kind_unsupported(const Model &m, JitKind kind) {
+    if (kind == JitKind::ContactWrench || kind == JitKind::RolloutContact)
+        return m.contacts.n_points > 0 ? "" : std::string(kind == JitKind::ContactWrench ? "contact_wrench" : "rollout_contact") +
+               ": the model carries no contact set (multibody_with_contacts makes a handle that does)";
     if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv && kind != JitKind::RolloutVjp) return "";
     const char *name = kind == JitKind::RneaDeriv ? "rnea_deriv" : kind == JitKind::FdDeriv ? "fd_deriv" : "rollout_vjp";
     if (!m.serial_revolute())
@@ -274,9 +279,27 @@ JitVariant jit_resolve(const Model &model, JitKind kind, bool f64, uint32_t B, b
     return v;
 }
 
+// The contact set as key text: a different set is a different kernel (exact values, hex floats).
+static std::string contact_key(const ContactSet &c) {
+    char buf[32];
+    std::string s = ":c" + std::to_string(c.n_points);
+    auto add = [&](double x) {
+        std::snprintf(buf, sizeof buf, ",%a", x);
+        s += buf;
+    };
+    for (int p = 0; p < c.n_points; ++p) {
+        s += "," + std::to_string(c.link[p]);
+        for (int k = 0; k < 3; ++k) add(c.point[p][k]);
+    }
+    for (int k = 0; k < 3; ++k) add(c.normal[k]);
+    for (double x : {c.offset, c.stiffness, c.damping, c.friction, c.slip_velocity}) add(x);
+    return s;
+}
+
 std::string jit_key(const Model &m, const JitVariant &v) {
     const JitKind kind = v.kind;
     const bool f64 = v.f64;
+    const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact;
     // ":w" the policy's target, ":W" the raw knob (-1 lets jit_compile rebuild at the occupancy cliff)
     return ":k" + std::to_string((int)kind) + (f64 ? ":f64" : ":f32") + (v.fast ? ":fast" : ":precise") + ":nt" +
            std::to_string(jit_nt(kind)) + ":w" + std::to_string(jit_waves(kind, f64, m.n)) + ":W" +
@@ -287,7 +310,7 @@ std::string jit_key(const Model &m, const JitVariant &v) {
            std::to_string(kind == JitKind::Rnea ? tuning().rnea_park.load() : 0) + ":e" +
            std::to_string(kind == JitKind::Rnea ? tuning().rnea_rev.load() : 0) + ":a" +
            std::to_string(tuning().kernarg_preload.load()) + ":q" + std::to_string(v.pack) + ":st" +
-           std::to_string(v.tail) + ":n" + std::to_string(v.nt);
+           std::to_string(v.tail) + ":n" + std::to_string(v.nt) + (contact ? contact_key(m.contacts) : std::string());
 }
 
 int code_vgprs(const std::vector<char> &code) {
@@ -326,7 +349,12 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const bool vjp = kind == JitKind::RolloutVjp;  // the rollout's adjoint: fd_deriv's scope and link forces
     const bool ext = kind == JitKind::RneaExt || kind == JitKind::FdExt;  // external link wrenches (ext_body.hip.hpp)
     const bool lk = kind == JitKind::LinkPose || kind == JitKind::LinkVel;  // every link's kinematics (link_kin_body.hip.hpp)
-    if ((deriv || vjp) && !jit_kind_unsupported(m, kind).empty()) return "";
+    // the contact set's wrench / the fused rollout under it (contact_body.hip.hpp).  RolloutContact
+    // deliberately takes none of Rollout's tuned build rules below (no-hoist / machine LICM off, the
+    // guard anchor below nine links, opaque constants, the fp64 4-wave target): each was adopted on an
+    // A/B measurement of that kernel, none has been measured for this one.
+    const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact;
+    if ((deriv || vjp || contact) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
         double *c = &pk[(size_t)i * kLinkStride];
@@ -368,7 +396,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     // 131 instead of 125 VGPRs (3 waves/SIMD instead of 4), and all its grid forms (pairs,
     // single tail, one per lane below 2^19) must stay bit-identical to each other.
     const bool dyn = kind == JitKind::Rnea || kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd ||
-                     deriv || vjp || ext;
+                     deriv || vjp || ext || kind == JitKind::RolloutContact;
     // jit_variant bit 16384 (A/B): the centre-of-mass form for the fp64 RNEA too
     // rnea_lane_rev: the fp64 RNEA of serial chains longer than 8 links, whose per-link forces
     // hold one wave per SIMD (12 links 264 VGPRs, 30 links 496) and do not fit LDS either
@@ -446,7 +474,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         }
         o << "};\n";
     }
-    o << (lk                                                ? "#include \"link_kin_body.hip.hpp\"\n"
+    o << (contact                                           ? "#include \"contact_body.hip.hpp\"\n"
+          : lk                                              ? "#include \"link_kin_body.hip.hpp\"\n"
           : ext                                             ? "#include \"ext_body.hip.hpp\"\n"
           : vjp                                            ? "#include \"rollout_vjp_body.hip.hpp\"\n"
           : deriv                                           ? "#include \"rnea_deriv_body.hip.hpp\"\n"
@@ -487,11 +516,44 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         for (size_t k = 0; k < pk.size(); ++k) o << "  " << literal(pk[k], f64) << ",\n";
     }
     o << "};\n";
-    if (ext || lk) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
+    if (ext || lk || contact) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
         const std::vector<double> ra = m.axis_frames();
         o << "static __device__ constexpr T kExtRa[" << ra.size() << "] = {\n";
         for (size_t k = 0; k < ra.size(); ++k) o << "  " << literal(snap(ra[k]), f64) << ",\n";
         o << "};\n";
+    }
+    if (contact) {
+        // the contact set as compile-time constants: a point's link and position, the plane, the
+        // law's parameters; kSlotOf[j] is link j's rank among the links that carry points (-1: none)
+        const ContactSet &c = m.contacts;
+        std::vector<int> slot_of(m.n, -1);
+        int slots = 0;
+        for (int j = 0; j < m.n; ++j)
+            for (int p = 0; p < c.n_points; ++p)
+                if (c.link[p] == j) {
+                    slot_of[j] = slots++;
+                    break;
+                }
+        o << "static __device__ constexpr int kConLink[" << c.n_points << "] = {";
+        for (int p = 0; p < c.n_points; ++p) o << (p ? ", " : "") << c.link[p];
+        o << "};\nstatic __device__ constexpr int kConSlotOf[N] = {";
+        for (int j = 0; j < m.n; ++j) o << (j ? ", " : "") << slot_of[j];
+        o << "};\nstatic __device__ constexpr T kConPoint[" << 3 * c.n_points << "] = {";
+        for (int p = 0; p < c.n_points; ++p)
+            for (int k = 0; k < 3; ++k) o << (p + k ? ", " : "") << literal(c.point[p][k], f64);
+        o << "};\nstatic __device__ constexpr T kConNormal[3] = {" << literal(snap(c.normal[0]), f64) << ", "
+          << literal(snap(c.normal[1]), f64) << ", " << literal(snap(c.normal[2]), f64) << "};\n";
+        o << "struct Con {\n  static constexpr int kSlots = " << slots << ";\n"
+          << "  static constexpr int points() { return " << c.n_points << "; }\n"
+             "  static constexpr int link(int p) { return kConLink[p]; }\n"
+             "  static constexpr int slot_of(int j) { return kConSlotOf[j]; }\n"
+             "  static constexpr T point(int p, int k) { return kConPoint[3 * p + k]; }\n"
+             "  static constexpr T normal(int k) { return kConNormal[k]; }\n"
+          << "  static constexpr T offset() { return " << literal(c.offset, f64) << "; }\n"
+          << "  static constexpr T stiffness() { return " << literal(c.stiffness, f64) << "; }\n"
+          << "  static constexpr T damping() { return " << literal(c.damping, f64) << "; }\n"
+          << "  static constexpr T friction() { return " << literal(c.friction, f64) << "; }\n"
+          << "  static constexpr T slip_velocity() { return " << literal(c.slip_velocity, f64) << "; }\n};\n";
     }
     // ---- the kernel: one signature helper, one prologue per lane form
     const std::string head = std::string("extern \"C\" __global__ __launch_bounds__(256) ") +
@@ -610,6 +672,19 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         else
             o << "  rbamd::dev::rnea_ext_lane<T, N, " << F
               << ", Topo>(kModel, kExtRa, q + o, qd + o, qdd + o, fext + o, tau + o, threadIdx.x, ld);\n}\n";
+    } else if (kind == JitKind::ContactWrench) {
+        // one configuration per lane on SoA rows: fext [6 N][ld], cforce [3 P][ld]
+        sig("const T *__restrict__ q, const T *__restrict__ qd, T *__restrict__ fext, T *__restrict__ cforce, "
+            "uint32_t B, int64_t ld, int64_t bs");
+        o << lane_prologue << "  rbamd::dev::contact_wrench_lane<T, N, " << F
+          << ", Topo, Con>(kModel, kExtRa, q + o, qd + o, fext + o, cforce + o, threadIdx.x, ld);\n}\n";
+    } else if (kind == JitKind::RolloutContact) {
+        sig(rollout_params);
+        o << "  __shared__ rbamd::dev::RolloutShared<T, N> sh;\n";
+        o << lane_guard;
+        o << "  rbamd::dev::rollout_contact_lane<T, N, " << F << ", Topo, "
+          << (jit_fd_form(m, JitKind::Rollout) == 2 ? "true" : "false")
+          << ", Con>(kModel, kExtRa, q, qd, tau_seq, dt, K, traj, b, ld, sh);\n}\n";
     } else if (lk) {
         // one configuration per lane on SoA rows: pos [3 N][ld] and rot [9 N][ld], or vel [6 N][ld]
         if (kind == JitKind::LinkVel) {

@@ -39,11 +39,16 @@ namespace rbamd {
 // LinkPose / LinkVel: pose / spatial velocity of every link in its URDF link frame
 // (link_kin_body.hip.hpp), every model, hipRTC only, one configuration per lane on SoA rows.
 // Internal too: multibody_link_kin_jit_source / _compile.
+// ContactWrench / RolloutContact: the contact set's wrench, and the fused rollout under it
+// (contact_body.hip.hpp), every model that carries a contact set (Model::contacts), hipRTC only, one
+// configuration per lane on SoA rows; the set is compiled in and part of jit_key.  RolloutContact's
+// forward dynamics follows jit_fd_form(m, JitKind::Rollout).  Internal too:
+// multibody_contact_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
-    RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13
+    RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13, ContactWrench = 14, RolloutContact = 15
 };
-constexpr int kJitKinds = 14;
+constexpr int kJitKinds = 16;
 constexpr int kJitPublicKinds = 9;
 
 // Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds and the

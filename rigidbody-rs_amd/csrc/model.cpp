@@ -369,8 +369,42 @@ Model Model::from_urdf_text(const std::string &xml, unsigned flags) {
     return m;
 }
 
+std::string ContactSet::refusal(int n) const {
+    if (n_points < 1 || n_points > kContactMaxPoints) return "contact model: n_points must be 1.." + std::to_string(kContactMaxPoints);
+    auto finite3 = [](const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    for (int p = 0; p < n_points; ++p) {
+        if (link[p] < 0 || link[p] >= n)
+            return "contact model: link[" + std::to_string(p) + "] is outside 0.." + std::to_string(n - 1);
+        if (!finite3(point[p])) return "contact model: point[" + std::to_string(p) + "] is not finite";
+    }
+    if (!finite3(normal)) return "contact model: normal is not finite";
+    const double nn = std::sqrt(normal[0] * normal[0] + normal[1] * normal[1] + normal[2] * normal[2]);
+    if (!(std::fabs(nn - 1.0) <= 1e-6)) return "contact model: normal is not a unit vector";
+    if (!std::isfinite(offset)) return "contact model: offset is not finite";
+    if (!std::isfinite(stiffness) || stiffness < 0) return "contact model: stiffness must be finite and >= 0";
+    if (!std::isfinite(damping) || damping < 0) return "contact model: damping must be finite and >= 0";
+    if (!std::isfinite(friction) || friction < 0) return "contact model: friction must be finite and >= 0";
+    if (!std::isfinite(slip_velocity) || !(slip_velocity > 0)) return "contact model: slip_velocity must be finite and > 0";
+    return "";
+}
+
 std::vector<double> Model::blob() const {
-    std::vector<double> b(kBlobHeader + (size_t)n * kBlobPerLink, 0.0);
+    std::vector<double> b(kBlobHeader + (size_t)n * kBlobPerLink + (size_t)contacts.blob_size(), 0.0);
+    if (contacts.n_points > 0) {  // the tail; a model without a contact set has none
+        double *t = &b[kBlobHeader + (size_t)n * kBlobPerLink];
+        const ContactSet &c = contacts;
+        *t++ = (double)c.n_points;
+        for (int p = 0; p < c.n_points; ++p) {
+            *t++ = (double)c.link[p];
+            for (int k = 0; k < 3; ++k) *t++ = c.point[p][k];
+        }
+        for (int k = 0; k < 3; ++k) *t++ = c.normal[k];
+        *t++ = c.offset;
+        *t++ = c.stiffness;
+        *t++ = c.damping;
+        *t++ = c.friction;
+        *t++ = c.slip_velocity;
+    }
     b[0] = kBlobMagic;
     b[1] = 3.0;
     b[2] = (double)n;
@@ -400,10 +434,32 @@ Model Model::from_blob(const double *b, int64_t len) {
     if (!b || len < kBlobHeader || b[0] != kBlobMagic || b[1] != 3.0)
         throw std::runtime_error("not a rigidbody model blob (version 3)");
     const int n = (int)b[2];
-    if (n < 1 || len != kBlobHeader + (int64_t)n * kBlobPerLink)
-        throw std::runtime_error("model blob has the wrong length");
+    const int64_t base = kBlobHeader + (int64_t)n * kBlobPerLink;
+    if (n < 1 || len < base) throw std::runtime_error("model blob has the wrong length");
     Model m;
     m.n = n;
+    if (len != base) {  // the contact set's tail
+        const double *t = b + base;
+        ContactSet &c = m.contacts;
+        const double np = t[0];
+        if (!(np >= 1 && np <= kContactMaxPoints) || np != (double)(int)np || len != base + 9 + 4 * (int64_t)np)
+            throw std::runtime_error("model blob has the wrong length");
+        c.n_points = (int)np;
+        ++t;
+        for (int p = 0; p < c.n_points; ++p) {
+            c.link[p] = (t[0] >= 0 && t[0] < n && t[0] == (double)(int)t[0]) ? (int)t[0] : -1;
+            for (int k = 0; k < 3; ++k) c.point[p][k] = t[1 + k];
+            t += 4;
+        }
+        for (int k = 0; k < 3; ++k) c.normal[k] = *t++;
+        c.offset = *t++;
+        c.stiffness = *t++;
+        c.damping = *t++;
+        c.friction = *t++;
+        c.slip_velocity = *t++;
+        const std::string why = c.refusal(n);
+        if (!why.empty()) throw std::runtime_error("model blob: " + why);
+    }
     m.pairing_matches_child = b[3] != 0.0;
     if (!(b[4] >= 0.0 && b[4] <= (double)kModelFlagsAll && b[4] == (double)(unsigned)b[4]))
         throw std::runtime_error("model blob has bad flags");

@@ -18,7 +18,7 @@
 namespace rbamd {
 
 constexpr int kBlobHeader = 5;    // magic, version, n, index-pairing flag, model flags
-constexpr int kBlobPerLink = 38;  // see Model::blob
+constexpr int kBlobPerLink = 38;  // see Model::blob (a model with a contact set appends ContactSet::blob_size)
 constexpr double kBlobMagic = 20250224.0;
 
 struct LinkModel {
@@ -56,11 +56,30 @@ enum : unsigned {
     kModelFlagsAll = 7u,
 };
 
+// Compliant ground contact (contact_body.hip.hpp; rigidbody_batch.h rb_contact_model): points fixed
+// to moving links, one plane in the base frame, the Hunt-Crossley / regularised-friction law's four
+// parameters.  Model data: the model-specialised kernels compile it in.
+constexpr int kContactMaxPoints = 16;
+struct ContactSet {
+    int n_points = 0;  // 0: the model carries no contact set
+    int link[kContactMaxPoints] = {};
+    double point[kContactMaxPoints][3] = {};  // in the link's URDF link frame
+    double normal[3] = {0, 0, 1};
+    double offset = 0;
+    double stiffness = 0, damping = 0, friction = 0, slip_velocity = 1;
+
+    // blob tail: n_points, then (link, x, y, z) per point, normal, offset, the four parameters
+    int64_t blob_size() const { return n_points > 0 ? 9 + 4 * (int64_t)n_points : 0; }
+    // Why a model of n links refuses this set, naming the field (empty: it is accepted).
+    std::string refusal(int n) const;
+};
+
 struct Model {
     int n = 0;
     std::vector<LinkModel> links;
     bool pairing_matches_child = true;
     unsigned flags = 0;
+    ContactSet contacts;
 
     // throws std::runtime_error
     static Model from_urdf_text(const std::string &xml, unsigned flags = 0);

@@ -107,18 +107,29 @@ _SIGNATURES = {
     "multibody_link_vel": (_int, [_vp] + [_dp] * 3),
     "multibody_link_kin_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
     "multibody_link_kin_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
+    # compliant ground contact: the handle that carries a set, its getter; one configuration
+    # (handle, q, qd, fext, cforce) / (handle, q, qd, tau_seq, dt, K, traj); inspection (handle,
+    # rollout, f64, batch, ...)
+    "multibody_with_contacts": (_vp, [_vp, _vp]),
+    "multibody_contact_model": (_int, [_vp, _vp]),
+    "multibody_contact_wrench": (_int, [_vp] + [_dp] * 4),
+    "multibody_rollout_contact": (_int, [_vp, _dp, _dp, _dp, _dbl, _int, _dp]),
+    "multibody_contact_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
+    "multibody_contact_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
 }
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
 _ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7,
-           "rnea_ext": 5, "fd_ext": 5, "link_pose": 3, "link_vel": 3}
+           "rnea_ext": 5, "fd_ext": 5, "link_pose": 3, "link_vel": 3, "contact_wrench": 4}
 for _t in ("f32", "f64"):
     for _k, _n in _ARRAYS.items():
         _SIGNATURES[f"multibody_{_k}_batch_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _i64, _vp])
-        if not _k.endswith(("_deriv", "_ext")) and not _k.startswith("link_"):
+        if not _k.endswith(("_deriv", "_ext")) and not _k.startswith(("link_", "contact_")):
             _SIGNATURES[f"multibody_{_k}_batch_tiled_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _vp])
         if _k not in ("crba", "fwd_kin", "jac"):
             _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
     _SIGNATURES[f"multibody_rollout_batch_{_t}"] = (_int, [_vp, _vp, _vp, _vp, _dbl, _int, _vp, _i64, _i64, _vp])
+    _SIGNATURES[f"multibody_rollout_contact_batch_{_t}"] = _SIGNATURES[f"multibody_rollout_batch_{_t}"]
+    _SIGNATURES[f"multibody_rollout_contact_batch_host_{_t}"] = (_int, [_vp, _vp, _vp, _vp, _dbl, _int, _vp, _i64])
     # (handle, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau[, work], batch[, ld, stream])
     _SIGNATURES[f"multibody_rollout_vjp_batch_{_t}"] = (_int, [_vp] * 4 + [_dbl, _int] + [_vp] * 6 + [_i64, _i64, _vp])
     _SIGNATURES[f"multibody_rollout_vjp_batch_host_{_t}"] = (_int, [_vp] * 4 + [_dbl, _int] + [_vp] * 5 + [_i64])
@@ -132,6 +143,16 @@ for _name, (_res, _args) in _SIGNATURES.items():
 
 class RigidBodyError(RuntimeError):
     pass
+
+
+CONTACT_MAX_POINTS = 16
+
+
+class _ContactModel(ctypes.Structure):
+    """rb_contact_model (rigidbody_batch.h)."""
+    _fields_ = [("n_points", _int), ("link", _int * CONTACT_MAX_POINTS),
+                ("point", (_dbl * 3) * CONTACT_MAX_POINTS), ("normal", _dbl * 3), ("offset", _dbl),
+                ("stiffness", _dbl), ("damping", _dbl), ("friction", _dbl), ("slip_velocity", _dbl)]
 
 
 def last_error() -> str:
@@ -605,6 +626,168 @@ class Multibody:
     def link_vel_batch_host(self, q, qd, dtype=np.float64):
         """Blocking host form of link_vel_batch on numpy arrays."""
         return self._link_kin_host("link_vel", (q, qd), (6,), dtype)[0]
+
+    # ---- compliant ground contact (rigidbody_batch.h "compliant ground contact")
+    def with_contacts(self, links, points, normal=(0.0, 0.0, 1.0), offset=0.0, stiffness=2000.0, damping=0.5,
+                      friction=0.7, slip_velocity=0.01):
+        """multibody_with_contacts: a NEW Multibody, this model plus a contact set -- points[p] (in the
+        URDF link frame of moving link links[p]) against the plane normal . x = offset of the base
+        frame, with the Hunt-Crossley / regularised-friction law's stiffness [N/m], damping [s/m],
+        friction and slip_velocity [m/s].  This handle is not modified."""
+        links = [int(l) for l in links]
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        if len(links) != len(pts):
+            raise ValueError(f"{len(links)} links for {len(pts)} points")
+        cm = _ContactModel()
+        cm.n_points = len(links)
+        for p in range(min(len(links), CONTACT_MAX_POINTS)):
+            cm.link[p] = links[p]
+            for k in range(3):
+                cm.point[p][k] = pts[p, k]
+        for k in range(3):
+            cm.normal[k] = float(normal[k])
+        cm.offset, cm.stiffness, cm.damping = float(offset), float(stiffness), float(damping)
+        cm.friction, cm.slip_velocity = float(friction), float(slip_velocity)
+        return Multibody(_lib.multibody_with_contacts(self._h, ctypes.byref(cm)))
+
+    def contact_model(self):
+        """multibody_contact_model: the contact set as a dict (None: the model carries none)."""
+        cm = _ContactModel()
+        P = _lib.multibody_contact_model(self._h, ctypes.byref(cm))
+        if P < 0:
+            raise RigidBodyError(last_error())
+        if P == 0:
+            return None
+        return {"links": [cm.link[p] for p in range(P)],
+                "points": np.array([[cm.point[p][k] for k in range(3)] for p in range(P)]),
+                "normal": tuple(cm.normal[k] for k in range(3)), "offset": cm.offset, "stiffness": cm.stiffness,
+                "damping": cm.damping, "friction": cm.friction, "slip_velocity": cm.slip_velocity}
+
+    @property
+    def n_contacts(self) -> int:
+        P = _lib.multibody_contact_model(self._h, None)
+        if P < 0:
+            raise RigidBodyError(last_error())
+        return P
+
+    def contact_wrench(self, q, qd):
+        """multibody_contact_wrench: (fext [n, 6], cforce [P, 3]) of one configuration, on the calling
+        thread: the contact set's wrench on every link (its URDF link frame, [force; moment]) and the
+        force at every point (base frame)."""
+        q, qd = _dvec(q, self.n), _dvec(qd, self.n)
+        fext, cforce = np.empty(6 * self.n), np.empty(3 * max(self.n_contacts, 1))
+        _check(_lib.multibody_contact_wrench(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, fext, cforce)]),
+               "contact_wrench")
+        return fext.reshape(self.n, 6), cforce.reshape(-1, 3)[:self.n_contacts]
+
+    def rollout_contact(self, q, qd, tau_seq, dt):
+        """multibody_rollout_contact: K steps of one configuration on the calling thread; tau_seq
+        [K, n].  Returns (traj [K, n], q [n], qd [n]) -- the inputs are not modified."""
+        q, qd = _dvec(q, self.n).copy(), _dvec(qd, self.n).copy()
+        tau = np.ascontiguousarray(tau_seq, dtype=np.float64)
+        if tau.ndim != 2 or tau.shape[1] != self.n:
+            raise ValueError(f"tau_seq must be [K, {self.n}]")
+        traj = np.empty_like(tau)
+        _check(_lib.multibody_rollout_contact(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau)], float(dt),
+                                              tau.shape[0], traj.ctypes.data_as(_dp)), "rollout_contact")
+        return traj, q, qd
+
+    def contact_jit_source(self, rollout=False, f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the contact_wrench (rollout=False) / rollout_contact kernel
+        (multibody_contact_jit_source)."""
+        a = (self._h, int(bool(rollout)), int(bool(f64)), int(batch))
+        n = _lib.multibody_contact_jit_source(*a, None, 0)
+        if n < 0:
+            raise RigidBodyError(last_error())
+        buf = ctypes.create_string_buffer(n + 1)
+        _lib.multibody_contact_jit_source(*a, buf, n + 1)
+        return buf.value.decode()
+
+    def contact_jit_compile(self, rollout=False, f64=False, arch="gfx950", batch=1 << 20) -> int:
+        r = _lib.multibody_contact_jit_compile(self._h, int(bool(rollout)), int(bool(f64)), int(batch), arch.encode())
+        if r < 0:
+            raise RigidBodyError(last_error())
+        return r
+
+    def contact_wrench_batch(self, q, qd, fext=None, cforce=None, stream=None):
+        """multibody_contact_wrench_batch_*: q, qd [n, B] -> (fext [6 n, B], cforce [3 P, B]); fext as
+        rnea_ext_batch / fd_ext_batch take it, row 3 p + c of cforce component c of the force at
+        point p in the base frame."""
+        q = _soa(q, self.n, "q")
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        qd = _soa(qd, self.n, "qd", q.dtype, B)
+        res = []
+        for t, name, rows in ((fext, "fext", 6 * self.n), (cforce, "cforce", 3 * max(self.n_contacts, 1))):
+            if t is None:
+                t = torch.empty((rows, _ld(q)), dtype=q.dtype, device=q.device)[:, :B]
+            else:
+                _soa(t, rows, name, q.dtype, B)
+            res.append(t)
+        live = [q, qd] + res
+        ld = _same_ld(live)
+        dev = _one_device(live)
+        fn = getattr(_lib, f"multibody_contact_wrench_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, *[t.data_ptr() for t in live], B, ld, _stream_ptr(stream, dev)), "contact_wrench_batch")
+        return res[0], res[1]
+
+    def rollout_contact_batch(self, q, qd, tau_seq, dt, traj=None, stream=None):
+        """multibody_rollout_contact_batch_*: K fused steps of fd_ext under the contact set, in place on
+        q and qd ([n, B] CUDA tensors); tau_seq [K, n, B].  Returns the trajectory [K, n, B] of q
+        (allocated here unless given).  Rows may be longer than B: every array -- tau_seq and traj as
+        [K n] rows -- shares one leading dimension."""
+        q = _soa(q, self.n, "q")
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        qd = _soa(qd, self.n, "qd", q.dtype, B)
+        ld = _same_ld((q, qd))
+
+        def rows(t, name):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[1:] != (self.n, B) or t.dtype != q.dtype:
+                raise ValueError(f"{name} must be [K, {self.n}, {B}] of the state's dtype")
+            if t.numel() and B > 1 and (t.stride(2) != 1 or t.stride(1) != ld or t.stride(0) != self.n * ld):
+                raise ValueError(f"{name} must be [K n] rows of the state's leading dimension ({ld})")
+            return t
+
+        tau_seq = rows(tau_seq, "tau_seq")
+        K = tau_seq.shape[0]
+        if traj is None:
+            traj = torch.empty((K, self.n, max(ld, 1)), dtype=q.dtype, device=q.device)[:, :, :B]
+        elif rows(traj, "traj").shape[0] != K:
+            raise ValueError(f"traj must have {K} steps")
+        dev = _one_device((q, qd, tau_seq, traj))
+        fn = getattr(_lib, f"multibody_rollout_contact_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau_seq.data_ptr(), float(dt), int(K), traj.data_ptr(), B,
+                      max(ld, B, 1), _stream_ptr(stream, dev)), "rollout_contact_batch")
+        return traj
+
+    def contact_wrench_batch_host(self, q, qd, dtype=np.float64):
+        """Blocking host form of contact_wrench_batch on numpy arrays -> (fext, cforce)."""
+        q, qd = _host_soa((q, qd), self.n, dtype)
+        B = q.shape[1]
+        fext = np.empty((6 * self.n, B), dtype=q.dtype)
+        cforce = np.empty((3 * max(self.n_contacts, 1), B), dtype=q.dtype)
+        fn = getattr(_lib, f"multibody_contact_wrench_batch_host_{'f32' if q.dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in (q, qd, fext, cforce)], B), "contact_wrench_batch_host")
+        return fext, cforce
+
+    def rollout_contact_batch_host(self, q, qd, tau_seq, dt, dtype=np.float64):
+        """Blocking host form of rollout_contact_batch on numpy arrays; tau_seq [K, n, B].  Returns
+        (traj [K, n, B], q [n, B], qd [n, B]) -- the inputs are not modified."""
+        q, qd = (a.copy() for a in _host_soa((q, qd), self.n, dtype))
+        B = q.shape[1]
+        tau = np.ascontiguousarray(tau_seq, dtype=q.dtype)
+        if tau.ndim != 3 or tau.shape[1:] != (self.n, B):
+            raise ValueError(f"tau_seq must be [K, {self.n}, {B}]")
+        traj = np.empty_like(tau)
+        fn = getattr(_lib, f"multibody_rollout_contact_batch_host_{'f32' if q.dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, q.ctypes.data, qd.ctypes.data, tau.ctypes.data, float(dt), tau.shape[0], traj.ctypes.data, B),
+               "rollout_contact_batch_host")
+        return traj, q, qd
 
     # ------------------------------------------------------- batched, device [n, B]
     def _soa_call(self, kind, ins, outs, stream):

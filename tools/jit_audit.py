@@ -5,6 +5,8 @@ instruction mix from the ISA.  CPU only (hipcc cross-compiles).
 usage: python tools/jit_audit.py KIND {f32,f64} [DOF] [--batch B] [--tiled]
        KIND in rnea fd crba rollout fwd_kin jac; the kernel a launch of B configurations takes
        (default 2^20, SoA), as multibody_jit_source_ex resolves it
+       KIND in contact_wrench rollout_contact: the contact kernels (multibody_contact_jit_source) of
+       the model with two points on its last link
 """
 import collections
 import os
@@ -30,7 +32,11 @@ def main():
     a = ap.parse_args()
     kind, dt, dof = a.kind, a.dt, a.dof
     mb = ffi.Multibody.new() if dof == 7 else ffi.Multibody.from_urdf_string(chains.synthetic_chain_urdf(dof))
-    src = mb.jit_source(dt == "f64", kind, batch=a.batch, tiled=a.tiled)
+    if kind in ("contact_wrench", "rollout_contact"):
+        mb = mb.with_contacts([mb.n - 1] * 2, [[0.05, 0.0, 0.1], [-0.05, 0.0, 0.1]], offset=0.4)
+        src = mb.contact_jit_source(kind == "rollout_contact", dt == "f64", batch=a.batch)
+    else:
+        src = mb.jit_source(dt == "f64", kind, batch=a.batch, tiled=a.tiled)
     d = f"/tmp/jit_audit_{kind}_{dt}_{dof}_{a.batch}{'_t' if a.tiled else ''}"
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, "k.hip")
