@@ -709,6 +709,84 @@ int multibody_rollout_contact(const Multibody *mb, double *q, double *qd, const 
 int multibody_contact_jit_source(const Multibody *mb, int rollout, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_contact_jit_compile(const Multibody *mb, int rollout, int f64, int64_t batch, const char *arch);
 
+/* ---- reverse-mode gradient of the fused contact rollout --------------------------- */
+/* multibody_rollout_vjp_* for a handle that carries a contact set: the vector-Jacobian product of
+ * K steps of multibody_rollout_contact_batch_* on the mass-matrix forward dynamics, one launch.
+ *   fext_k = contact(q_k, v_k)            (the law above, unchanged)
+ *   a_k = fd_ext(q_k, v_k, tau_k, fext_k)     v_{k+1} = v_k + dt a_k     q_{k+1} = q_k + dt v_{k+1}
+ *   L = sum_k gq[k] . q_{k+1} + gqd[k] . v_{k+1}
+ * Arguments, layout, cotangent convention, outputs (g_q0, g_qd0, g_tau) and the workspace
+ * (work [K][2n][ld]) are those of multibody_rollout_vjp_batch_*, argument for argument.
+ *
+ * Law of the derivative.  With T(q, v, a) = rnea(q, v, a) - sum_j J_j(q)^T fext_j(q, v), the adjoint
+ * step of multibody_rollout_vjp_* runs with rnea replaced by T (total derivatives in q and v, a_k
+ * held).  The law is continuous and piecewise smooth; its two max(., 0) take the derivative of the
+ * branch the forward code's own comparison selects (gap = d - nhat . x_p > 0, and
+ * k phi (1 + c phid) > 0): a point that does not push (f_n = 0) contributes exactly zero, also at
+ * a kink, where the function has one-sided derivatives only.  Friction (mu > 0) is differentiated
+ * through its regularisation; mu == 0 folds those terms away.  The contact terms are evaluated in
+ * reverse mode (contact_vjp_body.hip.hpp): O(n + P) work per step beside the column sweeps.
+ *
+ * Checks, in order: as multibody_rollout_vjp_batch_* (handle, batch >= 0, ld >= batch, batch == 0
+ * RB_OK, K < 0 / K == 0 RB_ERR_ARG, a NULL array RB_ERR_NULL, an aliased output or workspace
+ * RB_ERR_ARG), then a handle without a contact set RB_ERR_UNSUPPORTED (rb_last_error() names
+ * multibody_with_contacts), then the scope.  Batches are split at 2^28 per launch.
+ *
+ * Scope: multibody_rollout_vjp_*'s -- serial revolute chains (z-axis or RB_MODEL_GENERAL_AXES) up to
+ * 12 links; kinematic trees, prismatic joints, a floating base and longer chains return
+ * RB_ERR_UNSUPPORTED and rb_last_error() names the condition, as does hipRTC disabled or failed
+ * (with the log).  SoA rows only.
+ *
+ * Relation to multibody_rollout_contact_batch_*: the trajectory differentiated is the contact
+ * rollout of the mass-matrix forward dynamics.  For chains of 9 to 12 links
+ * multibody_rollout_contact_batch_* integrates the articulated-body form instead, so the two
+ * trajectories agree to rounding, not bit for bit.
+ *
+ * Input domain: q_k, v_k, tau_k and the contact wrench are checked at every step, all of them before
+ * the first store; a configuration that leaves the domain at any step gets NaN in every element of
+ * g_q0, g_qd0 and g_tau, the others are unaffected.  The cotangents are NOT checked.
+ *
+ * Accuracy (tests/test_contact_vjp_host.py, tests/test_gpu_contact_vjp.py; reference
+ * tests/contact_vjp_ref.py: Richardson central differences, h = 2e-3, of a rollout assembled from the
+ * reference contact law and the fp64 oracle's forward dynamics, along a unit direction, dt = 1e-3,
+ * K = 3, about 40% of the points pushing): fp64 |<g, d> - ref| <= 1e-7 (1 + |ref|) wherever that
+ * reference is self-consistent to 1e-8 (a configuration that crosses a kink within the step is not);
+ * measured on the MI355X (B = 257, first 40 configurations, 37-38 qualify): 4.4e-10 FR3, 4.7e-10 on 12
+ * links, 1.3e-10 on the general-axis 7-link chain, and 4.4e-10 against differences of
+ * multibody_rollout_contact_batch_f64 itself (FR3).  The kernel agrees with the host form of the same
+ * lane body to 7.02e-13 relative (measured 7.01e-14, K = 3), a configuration with a point exactly on
+ * the plane aside (its branch is decided by the last bit).  fp32 against the fp64 kernel on the same
+ * fp32-rounded inputs, per output array and configuration, configurations within 1e-3 m of the plane or
+ * with |1 + c phid| < 1e-2 while penetrating aside (a rounding flip of the branch there is not an
+ * error; 2% of FR3's): max|d| <= 6e-4 (1 + max|ref|) -- 4x the measured maximum, 1.47e-4 (12 links;
+ * FR3 2.0e-5). */
+int multibody_rollout_contact_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd,
+                                            const float *tau_seq, double dt, int K, const float *gq,
+                                            const float *gqd, float *g_q0, float *g_qd0, float *g_tau, float *work,
+                                            int64_t batch, int64_t ld, void *stream);
+int multibody_rollout_contact_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd,
+                                            const double *tau_seq, double dt, int K, const double *gq,
+                                            const double *gqd, double *g_q0, double *g_qd0, double *g_tau,
+                                            double *work, int64_t batch, int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch); the workspace is internal. */
+int multibody_rollout_contact_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd,
+                                                 const float *tau_seq, double dt, int K, const float *gq,
+                                                 const float *gqd, float *g_q0, float *g_qd0, float *g_tau,
+                                                 int64_t batch);
+int multibody_rollout_contact_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
+                                                 const double *tau_seq, double dt, int K, const double *gq,
+                                                 const double *gqd, double *g_q0, double *g_qd0, double *g_tau,
+                                                 int64_t batch);
+/* One configuration, fp64, [K][n] arrays, on the calling thread: the same lane body compiled for
+ * the host, no GPU involved (an FMA3 / AVX2 CPU, else RB_ERR_UNSUPPORTED). */
+int multibody_rollout_contact_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                  double dt, int K, const double *gq, const double *gqd, double *g_q0,
+                                  double *g_qd0, double *g_tau);
+/* Inspection of that kernel (no kind number), as multibody_contact_jit_source / _compile: a model
+ * out of scope or without a contact set has the empty source / -RB_ERR_UNSUPPORTED. */
+int multibody_contact_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_contact_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

@@ -277,14 +277,19 @@ hipError_t launch_fd_deriv(const Multibody *mb, const T *q, const T *qd, const T
                       [&] { return no_generic(mb, "the dynamics derivatives run"); });
 }
 
-// The rollout's reverse-mode gradient (rollout_vjp_body.hip.hpp): a model-specialised kernel only,
-// SoA rows, as the derivatives above.
+rbamd::JitKind vjp_kind(bool contact) {
+    return contact ? rbamd::JitKind::RolloutContactVjp : rbamd::JitKind::RolloutVjp;
+}
+const char *vjp_name(bool contact) { return contact ? "rollout_contact_vjp" : "rollout_vjp"; }
+
+// The rollouts' reverse-mode gradients (rollout_vjp_body.hip.hpp; contact: contact_vjp_body.hip.hpp, the
+// same arguments): a model-specialised kernel only, SoA rows, as the derivatives above.
 template <typename T>
-hipError_t launch_rollout_vjp(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, T dt, int K, const T *gq,
+hipError_t launch_rollout_vjp(const Multibody *mb, bool contact, const T *q, const T *qd, const T *tau_seq, T dt, int K, const T *gq,
                               const T *gqd, T *g_q0, T *g_qd0, T *g_tau, T *work, uint32_t B, int64_t ld,
                               hipStream_t s) {
     void *args[] = {&q, &qd, &tau_seq, &dt, &K, &gq, &gqd, &g_q0, &g_qd0, &g_tau, &work, &B, &ld};
-    return launch_any(mb, rbamd::JitKind::RolloutVjp, sizeof(T) == 8, B, false, s, args,
+    return launch_any(mb, vjp_kind(contact), sizeof(T) == 8, B, false, s, args,
                       [&] { return no_generic(mb, "the rollout gradient runs"); });
 }
 
@@ -706,31 +711,34 @@ int rollout_batch(const Multibody *mb, T *q, T *qd, const T *tau_seq, double dt,
     });
 }
 
-// The rollout gradient's checks after handle / batch / ld and the empty-batch return: the step
-// count, then (`arrays`) every array present, no output or the workspace aliased, a model in scope.
-int vjp_steps_ok(int K) {
+// The rollout gradients' checks after handle / batch / ld and the empty-batch return: the step
+// count, then (`arrays`) every array present, no output or the workspace aliased, a model in scope
+// (contact: one that carries a contact set, checked just before the scope).
+int vjp_steps_ok(bool contact, int K) {
     if (K < 0) return set_err(RB_ERR_ARG, "negative step count");
-    if (K == 0) return set_err(RB_ERR_ARG, "rollout_vjp: K == 0 steps, nothing to differentiate");
+    if (K == 0) return set_err(RB_ERR_ARG, std::string(vjp_name(contact)) + ": K == 0 steps, nothing to differentiate");
     return RB_OK;
 }
 
 template <typename T>
-int vjp_args_ok(const Multibody *mb, std::initializer_list<const T *> in, std::initializer_list<const T *> out) {
+int vjp_args_ok(const Multibody *mb, bool contact, std::initializer_list<const T *> in,
+                std::initializer_list<const T *> out) {
     for (const T *p : out)
         if (!p) return set_err(RB_ERR_NULL, "NULL array");
-    return deriv_args_ok<T>(mb, rbamd::JitKind::RolloutVjp, "rollout_vjp", in, out);
+    return deriv_args_ok<T>(mb, vjp_kind(contact), vjp_name(contact), in, out);
 }
 
 template <typename T>
-int rollout_vjp_batch(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
+int rollout_vjp_batch(const Multibody *mb, bool contact, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
                       const T *gqd, T *g_q0, T *g_qd0, T *g_tau, T *work, int64_t batch, int64_t ld, void *stream) {
     auto args_ok = [&] {
-        if (int rc = vjp_steps_ok(K)) return rc;
-        return vjp_args_ok<T>(mb, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau, work});
+        if (int rc = vjp_steps_ok(contact, K)) return rc;
+        return vjp_args_ok<T>(mb, contact, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau, work});
     };
-    return batch_call<T>(mb, batch, ld, false, args_ok, "rollout_vjp launch", [&](const T *, ChunkAt at, uint32_t nb) {
+    return batch_call<T>(mb, batch, ld, false, args_ok, contact ? "rollout_contact_vjp launch" : "rollout_vjp launch",
+                         [&](const T *, ChunkAt at, uint32_t nb) {
         const int n = mb->model.n;  // tau_seq, gq, gqd, g_tau: K * n rows; work: 2 K n
-        return launch_rollout_vjp<T>(mb, at(q, n), at(qd, n), at(tau_seq, K * n), (T)dt, K, at(gq, K * n),
+        return launch_rollout_vjp<T>(mb, contact, at(q, n), at(qd, n), at(tau_seq, K * n), (T)dt, K, at(gq, K * n),
                                      at(gqd, K * n), at(g_q0, n), at(g_qd0, n), at(g_tau, K * n), at(work, 2 * K * n), nb,
                                      ld, (hipStream_t)stream);
     });
@@ -939,19 +947,19 @@ int rollout_contact_host(const Multibody *mb, T *q, T *qd, const T *tau_seq, dou
 }
 
 template <typename T>
-int rollout_vjp_host(const Multibody *mb, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
+int rollout_vjp_host(const Multibody *mb, bool contact, const T *q, const T *qd, const T *tau_seq, double dt, int K, const T *gq,
                      const T *gqd, T *g_q0, T *g_qd0, T *g_tau, int64_t batch) {
     // the step count comes before the arrays, as in the device form
     int rc = check_batch(mb, batch, batch);
     if (rc) return rc;
     if (batch == 0) return RB_OK;
-    if ((rc = vjp_steps_ok(K))) return rc;
+    if ((rc = vjp_steps_ok(contact, K))) return rc;
     const int64_t n = mb->model.n, kn = (int64_t)K * n;
     return host_call_rows<T, 5, 3>(
         mb, {q, qd, tau_seq, gq, gqd}, {n, n, kn, kn, kn}, {g_q0, g_qd0, g_tau}, {n, n, kn}, 2 * kn, false, batch,
-        [&] { return vjp_args_ok<T>(mb, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau}); },
+        [&] { return vjp_args_ok<T>(mb, contact, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau}); },
         [&](T **i, T **o, hipStream_t s) {
-            return rollout_vjp_batch<T>(mb, i[0], i[1], i[2], dt, K, i[3], i[4], o[0], o[1], o[2], o[3], batch, batch, s);
+            return rollout_vjp_batch<T>(mb, contact, i[0], i[1], i[2], dt, K, i[3], i[4], o[0], o[1], o[2], o[3], batch, batch, s);
         });
 }
 }  // namespace
@@ -1194,10 +1202,10 @@ std::string shaped_source(const Multibody *mb, int kind, bool f64, int64_t batch
 
 // The rollout gradient's kernel has no public kind number: its two inspection entry points check
 // the handle, the batch and the model's scope here.
-int check_vjp_query(const Multibody *mb, int64_t batch) {
+int check_vjp_query(const Multibody *mb, bool contact, int64_t batch) {
     if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
     if (batch < 1) return set_err(RB_ERR_ARG, "batch must be positive");
-    return deriv_supported(mb, rbamd::JitKind::RolloutVjp);
+    return deriv_supported(mb, vjp_kind(contact));
 }
 
 // rc: the query's check; a kind with no kernel for this model (RB_ERR_UNSUPPORTED) has the empty source.
@@ -1281,7 +1289,11 @@ int multibody_jit_source_ex(const Multibody *mb, int kind, int f64, int64_t batc
 }
 
 int multibody_rollout_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap) {
-    return source_query(mb, check_vjp_query(mb, batch), (int)rbamd::JitKind::RolloutVjp, f64, batch, 0, buf, cap);
+    return source_query(mb, check_vjp_query(mb, false, batch), (int)vjp_kind(false), f64, batch, 0, buf, cap);
+}
+
+int multibody_contact_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_vjp_query(mb, true, batch), (int)vjp_kind(true), f64, batch, 0, buf, cap);
 }
 
 int64_t multibody_jit_compile(const Multibody *mb, int kind, int f64, const char *arch) {
@@ -1294,8 +1306,13 @@ int64_t multibody_jit_compile_ex(const Multibody *mb, int kind, int f64, int64_t
 }
 
 int64_t multibody_rollout_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch) {
-    if (int rc = check_vjp_query(mb, batch)) return -rc;
-    return compile_query(mb, (int)rbamd::JitKind::RolloutVjp, f64, batch, 0, arch);
+    if (int rc = check_vjp_query(mb, false, batch)) return -rc;
+    return compile_query(mb, (int)vjp_kind(false), f64, batch, 0, arch);
+}
+
+int64_t multibody_contact_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_vjp_query(mb, true, batch)) return -rc;
+    return compile_query(mb, (int)vjp_kind(true), f64, batch, 0, arch);
 }
 
 int multibody_ext_jit_source(const Multibody *mb, int fd, int f64, int64_t batch, char *buf, int64_t cap) {
@@ -1527,31 +1544,64 @@ int multibody_fd_deriv_batch_host_f64(const Multibody *mb, const double *q, cons
 int multibody_rollout_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq, double dt,
                                     int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0, float *g_tau,
                                     float *work, int64_t batch, int64_t ld, void *stream) {
-    return rollout_vjp_batch<float>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
+    return rollout_vjp_batch<float>(mb, false, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
 }
 int multibody_rollout_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
                                     double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
                                     double *g_tau, double *work, int64_t batch, int64_t ld, void *stream) {
-    return rollout_vjp_batch<double>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
+    return rollout_vjp_batch<double>(mb, false, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
 }
 int multibody_rollout_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq,
                                          double dt, int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0,
                                          float *g_tau, int64_t batch) {
-    return rollout_vjp_host<float>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
+    return rollout_vjp_host<float>(mb, false, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
 }
 int multibody_rollout_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
                                          double dt, int K, const double *gq, const double *gqd, double *g_q0,
                                          double *g_qd0, double *g_tau, int64_t batch) {
-    return rollout_vjp_host<double>(mb, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
+    return rollout_vjp_host<double>(mb, false, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
 }
 
 int multibody_rollout_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau_seq, double dt, int K,
                           const double *gq, const double *gqd, double *g_q0, double *g_qd0, double *g_tau) {
     if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
-    if (int rc = vjp_steps_ok(K)) return rc;
-    if (int rc = vjp_args_ok<double>(mb, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau})) return rc;
+    if (int rc = vjp_steps_ok(false, K)) return rc;
+    if (int rc = vjp_args_ok<double>(mb, false, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau})) return rc;
     if (!rbamd::host_rollout_vjp(mb->model, mb->pk64.data(), q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau))
         return set_err(RB_ERR_UNSUPPORTED, "rollout_vjp: the single-configuration form runs on the host and needs an "
+                                           "FMA3 / AVX2 CPU");
+    return RB_OK;
+}
+
+// ------------------------------------------------------------- gradient of the contact rollout
+int multibody_rollout_contact_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq, double dt,
+                                    int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0, float *g_tau,
+                                    float *work, int64_t batch, int64_t ld, void *stream) {
+    return rollout_vjp_batch<float>(mb, true, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
+}
+int multibody_rollout_contact_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                    double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
+                                    double *g_tau, double *work, int64_t batch, int64_t ld, void *stream) {
+    return rollout_vjp_batch<double>(mb, true, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, batch, ld, stream);
+}
+int multibody_rollout_contact_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau_seq,
+                                         double dt, int K, const float *gq, const float *gqd, float *g_q0, float *g_qd0,
+                                         float *g_tau, int64_t batch) {
+    return rollout_vjp_host<float>(mb, true, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
+}
+int multibody_rollout_contact_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau_seq,
+                                         double dt, int K, const double *gq, const double *gqd, double *g_q0,
+                                         double *g_qd0, double *g_tau, int64_t batch) {
+    return rollout_vjp_host<double>(mb, true, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, batch);
+}
+
+int multibody_rollout_contact_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau_seq, double dt, int K,
+                          const double *gq, const double *gqd, double *g_q0, double *g_qd0, double *g_tau) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = vjp_steps_ok(true, K)) return rc;
+    if (int rc = vjp_args_ok<double>(mb, true, {q, qd, tau_seq, gq, gqd}, {g_q0, g_qd0, g_tau})) return rc;
+    if (!rbamd::host_rollout_contact_vjp(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau))
+        return set_err(RB_ERR_UNSUPPORTED, "rollout_contact_vjp: the single-configuration form runs on the host and needs an "
                                            "FMA3 / AVX2 CPU");
     return RB_OK;
 }

@@ -19,6 +19,7 @@
 #include "crba_body.hip.hpp"
 #include "dofs.hpp"
 #include "contact_body.hip.hpp"
+#include "contact_vjp_body.hip.hpp"
 #include "ext_body.hip.hpp"
 #include "kernels.hpp"
 #include "link_kin_body.hip.hpp"
@@ -166,45 +167,78 @@ RB_HOST_FMA bool fd_deriv_fma(int n, const double *mdl, const double *q, const d
     }
 }
 
+// The model's contact set as contact_body's `Con`: run-time values, a slot per point at most.
 template <int N>
-RB_HOST_FMA bool rollout_vjp_fma_n(const double *mdl, const double *q, const double *qd, const double *tau_seq,
-                                   double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
-                                   double *g_tau, double *work) {
+struct HostCon {
+    static constexpr int kSlots = kContactMaxPoints;
+    const ContactSet &c;
+    int slot[N];
+    explicit HostCon(const ContactSet &set) : c(set) {
+        int slots = 0;
+        for (int j = 0; j < N; ++j) {
+            slot[j] = -1;
+            for (int p = 0; p < c.n_points && slot[j] < 0; ++p)
+                if (c.link[p] == j) slot[j] = slots++;
+        }
+    }
+    int points() const { return c.n_points; }
+    int link(int p) const { return c.link[p]; }
+    int slot_of(int j) const { return slot[j]; }
+    double point(int p, int k) const { return c.point[p][k]; }
+    double normal(int k) const { return c.normal[k]; }
+    double offset() const { return c.offset; }
+    double stiffness() const { return c.stiffness; }
+    double damping() const { return c.damping; }
+    double friction() const { return c.friction; }
+    double slip_velocity() const { return c.slip_velocity; }
+};
+
+// cs: the contact set of the contact rollout's gradient (contact_vjp_body.hip.hpp; ra its axis
+// frames), NULL for the contact-free rollout's.
+template <int N>
+RB_HOST_FMA bool rollout_vjp_fma_n(const ContactSet *cs, const double *mdl, const double *ra, const double *q,
+                                   const double *qd, const double *tau_seq, double dt, int K, const double *gq,
+                                   const double *gqd, double *g_q0, double *g_qd0, double *g_tau, double *work) {
     if constexpr (N <= kHostFdDerivMaxLinks) {
         double a[N], b[N];
         for (int j = 0; j < N; ++j) {
             a[j] = q[j];
             b[j] = qd[j];
         }
-        dev::rollout_vjp_eval<double, N, false>(
-            mdl, a, b, dt, K,
-            [&](int k, double(&tv)[N]) {
-                for (int j = 0; j < N; ++j) tv[j] = tau_seq[(size_t)k * N + j];
-            },
-            [&](int k, double(&x)[N], double(&y)[N]) {
-                for (int j = 0; j < N; ++j) {
-                    x[j] = gq[(size_t)k * N + j];
-                    y[j] = gqd[(size_t)k * N + j];
-                }
-            },
-            [&](int k, int r, double v) { work[(size_t)k * 2 * N + r] = v; }, [&](int k, int r) { return work[(size_t)k * 2 * N + r]; },
-            [&](int k, int j, double v) { g_tau[(size_t)k * N + j] = v; },
-            [&](int j, double x, double y) {
-                g_q0[j] = x;
-                g_qd0[j] = y;
-            });
+        auto load_tau = [&](int k, double(&tv)[N]) {
+            for (int j = 0; j < N; ++j) tv[j] = tau_seq[(size_t)k * N + j];
+        };
+        auto load_g = [&](int k, double(&x)[N], double(&y)[N]) {
+            for (int j = 0; j < N; ++j) {
+                x[j] = gq[(size_t)k * N + j];
+                y[j] = gqd[(size_t)k * N + j];
+            }
+        };
+        auto work_st = [&](int k, int r, double v) { work[(size_t)k * 2 * N + r] = v; };
+        auto work_ld = [&](int k, int r) { return work[(size_t)k * 2 * N + r]; };
+        auto out_tau = [&](int k, int j, double v) { g_tau[(size_t)k * N + j] = v; };
+        auto out_state = [&](int j, double x, double y) {
+            g_q0[j] = x;
+            g_qd0[j] = y;
+        };
+        if (cs)
+            dev::rollout_contact_vjp_eval<double, N, false, HostSerialTopo<N>>(
+                mdl, ra, HostCon<N>(*cs), a, b, dt, K, load_tau, load_g, work_st, work_ld, out_tau, out_state);
+        else
+            dev::rollout_vjp_eval<double, N, false>(mdl, a, b, dt, K, load_tau, load_g, work_st, work_ld, out_tau,
+                                                    out_state);
         return true;
     } else {
         return false;
     }
 }
 
-RB_HOST_FMA bool rollout_vjp_fma(int n, const double *mdl, const double *q, const double *qd, const double *tau_seq,
-                                 double dt, int K, const double *gq, const double *gqd, double *g_q0, double *g_qd0,
-                                 double *g_tau, double *work) {
+RB_HOST_FMA bool rollout_vjp_fma(int n, const ContactSet *cs, const double *mdl, const double *ra, const double *q,
+                                 const double *qd, const double *tau_seq, double dt, int K, const double *gq,
+                                 const double *gqd, double *g_q0, double *g_qd0, double *g_tau, double *work) {
     switch (n) {
 #define X(N) \
-    case N: return rollout_vjp_fma_n<N>(mdl, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work);
+    case N: return rollout_vjp_fma_n<N>(cs, mdl, ra, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work);
         RB_FOR_EACH_DOF(X)
 #undef X
         default: return false;
@@ -305,32 +339,6 @@ RB_HOST_FMA bool link_vel_fma(int n, const double *mdl, const double *ra, const 
     }
 }
 
-// The model's contact set as contact_body's `Con`: run-time values, a slot per point at most.
-template <int N>
-struct HostCon {
-    static constexpr int kSlots = kContactMaxPoints;
-    const ContactSet &c;
-    int slot[N];
-    explicit HostCon(const ContactSet &set) : c(set) {
-        int slots = 0;
-        for (int j = 0; j < N; ++j) {
-            slot[j] = -1;
-            for (int p = 0; p < c.n_points && slot[j] < 0; ++p)
-                if (c.link[p] == j) slot[j] = slots++;
-        }
-    }
-    int points() const { return c.n_points; }
-    int link(int p) const { return c.link[p]; }
-    int slot_of(int j) const { return slot[j]; }
-    double point(int p, int k) const { return c.point[p][k]; }
-    double normal(int k) const { return c.normal[k]; }
-    double offset() const { return c.offset; }
-    double stiffness() const { return c.stiffness; }
-    double damping() const { return c.damping; }
-    double friction() const { return c.friction; }
-    double slip_velocity() const { return c.slip_velocity; }
-};
-
 RB_HOST_FMA bool contact_wrench_fma(int n, const ContactSet &cs, const double *mdl, const double *ra, const double *q,
                                     const double *qd, double *fext, double *cforce) {
     switch (n) {
@@ -425,7 +433,15 @@ bool host_rollout_vjp(const Model &m, const double *pk, const double *q, const d
                       double *g_tau) {
     if (!host_eval_supported(m) || m.n > kHostFdDerivMaxLinks || K < 1) return false;
     std::vector<double> work((size_t)K * 2 * m.n);
-    return rollout_vjp_fma(m.n, pk, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work.data());
+    return rollout_vjp_fma(m.n, nullptr, pk, nullptr, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work.data());
+}
+
+bool host_rollout_contact_vjp(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                              const double *tau_seq, double dt, int K, const double *gq, const double *gqd,
+                              double *g_q0, double *g_qd0, double *g_tau) {
+    if (!host_eval_supported(m) || m.n > kHostFdDerivMaxLinks || K < 1 || m.contacts.n_points < 1) return false;
+    std::vector<double> work((size_t)K * 2 * m.n);
+    return rollout_vjp_fma(m.n, &m.contacts, pk, ra, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work.data());
 }
 
 bool host_rnea_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,

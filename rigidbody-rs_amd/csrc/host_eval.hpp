@@ -57,4 +57,10 @@ bool host_contact_wrench(const Model &m, const double *pk, const double *ra, con
 bool host_rollout_contact(const Model &m, const double *pk, const double *ra, double *q, double *qd,
                           const double *tau_seq, double dt, int K, double *traj);
 
+// Reverse-mode gradient of the K-step contact rollout (contact_vjp_body.hip.hpp): host_rollout_vjp's
+// scope and arrays, on a model that carries a contact set.
+bool host_rollout_contact_vjp(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                              const double *tau_seq, double dt, int K, const double *gq, const double *gqd,
+                              double *g_q0, double *g_qd0, double *g_tau);
+
 }  // namespace rbamd

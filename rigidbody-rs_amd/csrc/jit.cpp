@@ -149,8 +149,13 @@ std::string jit_kind_unsupported(const Model &m, JitKind kind) {
     if (kind == JitKind::ContactWrench || kind == JitKind::RolloutContact)
         return m.contacts.n_points > 0 ? "" : std::string(kind == JitKind::ContactWrench ? "contact_wrench" : "rollout_contact") +
                ": the model carries no contact set (multibody_with_contacts makes a handle that does)";
-    if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv && kind != JitKind::RolloutVjp) return "";
-    const char *name = kind == JitKind::RneaDeriv ? "rnea_deriv" : kind == JitKind::FdDeriv ? "fd_deriv" : "rollout_vjp";
+    if (kind == JitKind::RolloutContactVjp && m.contacts.n_points < 1)
+        return "rollout_contact_vjp: the model carries no contact set (multibody_with_contacts makes a handle that does)";
+    if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv && kind != JitKind::RolloutVjp &&
+        kind != JitKind::RolloutContactVjp)
+        return "";
+    const char *name = kind == JitKind::RneaDeriv ? "rnea_deriv" : kind == JitKind::FdDeriv ? "fd_deriv"
+                       : kind == JitKind::RolloutVjp ? "rollout_vjp" : "rollout_contact_vjp";
     if (!m.serial_revolute())
         return std::string(name) + ": no such kernel for this model: serial revolute chains only (kinematic trees, "
                "prismatic joints and a floating base are not supported)";
@@ -299,7 +304,8 @@ static std::string contact_key(const ContactSet &c) {
 std::string jit_key(const Model &m, const JitVariant &v) {
     const JitKind kind = v.kind;
     const bool f64 = v.f64;
-    const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact;
+    const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact ||
+                         kind == JitKind::RolloutContactVjp;
     // ":w" the policy's target, ":W" the raw knob (-1 lets jit_compile rebuild at the occupancy cliff)
     return ":k" + std::to_string((int)kind) + (f64 ? ":f64" : ":f32") + (v.fast ? ":fast" : ":precise") + ":nt" +
            std::to_string(jit_nt(kind)) + ":w" + std::to_string(jit_waves(kind, f64, m.n)) + ":W" +
@@ -339,21 +345,24 @@ static bool jit_no_licm(const Model &m, const JitVariant &v) {
 // independent FMAs into 2-wide operations whose register pairs cost more than the packed
 // arithmetic saves (FR3 fp32: 512 registers and 840 B of scratch per lane with it, 194 and none
 // without; fp64 380 / 386, no scratch either way).
-static bool jit_no_slp(const JitVariant &v) { return v.kind == JitKind::RolloutVjp; }
+static bool jit_no_slp(const JitVariant &v) {
+    return v.kind == JitKind::RolloutVjp || v.kind == JitKind::RolloutContactVjp;
+}
 
 std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const JitKind kind = v.kind;
     const bool f64 = v.f64;
     const int pack = v.pack;
     const bool deriv = kind == JitKind::RneaDeriv || kind == JitKind::FdDeriv;
-    const bool vjp = kind == JitKind::RolloutVjp;  // the rollout's adjoint: fd_deriv's scope and link forces
+    const bool cvjp = kind == JitKind::RolloutContactVjp;  // the contact rollout's adjoint (contact_vjp_body.hip.hpp)
+    const bool vjp = kind == JitKind::RolloutVjp || cvjp;  // the rollouts' adjoints: fd_deriv's scope and link forces
     const bool ext = kind == JitKind::RneaExt || kind == JitKind::FdExt;  // external link wrenches (ext_body.hip.hpp)
     const bool lk = kind == JitKind::LinkPose || kind == JitKind::LinkVel;  // every link's kinematics (link_kin_body.hip.hpp)
     // the contact set's wrench / the fused rollout under it (contact_body.hip.hpp).  RolloutContact
     // deliberately takes none of Rollout's tuned build rules below (no-hoist / machine LICM off, the
     // guard anchor below nine links, opaque constants, the fp64 4-wave target): each was adopted on an
     // A/B measurement of that kernel, none has been measured for this one.
-    const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact;
+    const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact || cvjp;
     if ((deriv || vjp || contact) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
@@ -474,7 +483,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         }
         o << "};\n";
     }
-    o << (contact                                           ? "#include \"contact_body.hip.hpp\"\n"
+    o << (cvjp                                              ? "#include \"contact_vjp_body.hip.hpp\"\n"
+          : contact                                         ? "#include \"contact_body.hip.hpp\"\n"
           : lk                                              ? "#include \"link_kin_body.hip.hpp\"\n"
           : ext                                             ? "#include \"ext_body.hip.hpp\"\n"
           : vjp                                            ? "#include \"rollout_vjp_body.hip.hpp\"\n"
@@ -712,13 +722,18 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
             o << "  rbamd::dev::rnea_deriv_lane<T, N, " << F
               << ">(kModel, q + o, qd + o, qdd + o, dq ? dq + o : nullptr, dqd ? dqd + o : nullptr, threadIdx.x, ld);\n}\n";
     } else if (vjp) {
-        // one configuration per lane on SoA rows, K steps forward then K back (rollout_vjp_body.hip.hpp)
+        // one configuration per lane on SoA rows, K steps forward then K back (rollout_vjp_body.hip.hpp,
+        // contact_vjp_body.hip.hpp)
         sig("const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ tau_seq, T dt, int K, "
             "const T *__restrict__ gq, const T *__restrict__ gqd, T *__restrict__ g_q0, T *__restrict__ g_qd0, "
             "T *__restrict__ g_tau, T *work, uint32_t B, int64_t ld");
         o << lane_guard;
-        o << "  rbamd::dev::rollout_vjp_lane<T, N, " << F
-          << ">(kModel, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, b, ld);\n}\n";
+        if (cvjp)
+            o << "  rbamd::dev::rollout_contact_vjp_lane<T, N, " << F
+              << ", Topo, Con>(kModel, kExtRa, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, b, ld);\n}\n";
+        else
+            o << "  rbamd::dev::rollout_vjp_lane<T, N, " << F
+              << ">(kModel, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau, work, b, ld);\n}\n";
     } else if (kind == JitKind::Rollout) {
         sig(rollout_params);
         if (pack == 4) {

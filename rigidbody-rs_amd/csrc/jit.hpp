@@ -44,11 +44,15 @@ namespace rbamd {
 // configuration per lane on SoA rows; the set is compiled in and part of jit_key.  RolloutContact's
 // forward dynamics follows jit_fd_form(m, JitKind::Rollout).  Internal too:
 // multibody_contact_jit_source / _compile.
+// RolloutContactVjp: the reverse-mode gradient of the contact rollout (contact_vjp_body.hip.hpp):
+// RolloutVjp's scope on a model that carries a contact set, the set compiled in and part of jit_key.
+// Internal too: multibody_contact_vjp_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
-    RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13, ContactWrench = 14, RolloutContact = 15
+    RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13, ContactWrench = 14, RolloutContact = 15,
+    RolloutContactVjp = 16
 };
-constexpr int kJitKinds = 16;
+constexpr int kJitKinds = 17;
 constexpr int kJitPublicKinds = 9;
 
 // Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds and the

@@ -47,13 +47,18 @@ RB_HD void vjp_step_fd(const T *mdl, const T (&qv)[N], const T (&qdv)[N], Tau &&
     fdh_solve<T, N>(H, Di, tv, C, [&](int j, T v) { av[j] = v; });
 }
 
-// qv, qdv: the initial state (overwritten).  load_tau(k, tv), load_g(k, gq, gqd): step k's rows;
+// The two sweeps over a step of the caller's: step(k, qv, qdv, cs, sn, H, Di, av, gd) leaves step k's
+// (cos, sin), the factors of H and a_k, every input of the step through gd; extra(qv, qdv, cs, sn, mu,
+// lq, lv), after the column sweeps, adds what the step's generalised force has beyond rnea (the
+// contact terms of contact_vjp_body.hip.hpp; nothing here).
+// qv, qdv: the initial state (overwritten).  load_g(k, gq, gqd): step k's rows;
 // work_st(k, r, v) / work_ld(k, r): row r < 2 N of step k's workspace; out_tau(k, j, v);
 // out_state(j, g_q0_j, g_qd0_j).  K >= 1.
-template <typename T, int N, bool FAST, typename LoadTau, typename LoadG, typename WorkSt, typename WorkLd,
+template <typename T, int N, typename Step, typename Extra, typename LoadG, typename WorkSt, typename WorkLd,
           typename OutTau, typename OutState>
-RB_HD void rollout_vjp_eval(const T *mdl, T (&qv)[N], T (&qdv)[N], T dt, int K, LoadTau &&load_tau, LoadG &&load_g,
-                            WorkSt &&work_st, WorkLd &&work_ld, OutTau &&out_tau, OutState &&out_state) {
+RB_HD void rollout_adjoint_eval(const T *mdl, T (&qv)[N], T (&qdv)[N], T dt, int K, Step &&step, Extra &&extra,
+                                LoadG &&load_g, WorkSt &&work_st, WorkLd &&work_ld, OutTau &&out_tau,
+                                OutState &&out_state) {
     InputGuard<T> gd;
     for (int k = 0; k + 1 < K; ++k) {
 #pragma unroll
@@ -62,7 +67,7 @@ RB_HD void rollout_vjp_eval(const T *mdl, T (&qv)[N], T (&qdv)[N], T dt, int K, 
             work_st(k, N + j, qdv[j]);
         }
         T cs[N], sn[N], H[N][N], Di[N], av[N];
-        vjp_step_fd<T, N, FAST>(mdl, qv, qdv, [&](T (&tv)[N]) { load_tau(k, tv); }, cs, sn, H, Di, av, gd);
+        step(k, qv, qdv, cs, sn, H, Di, av, gd);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             qdv[j] = fmadd(dt, av[j], qdv[j]);
@@ -82,7 +87,7 @@ RB_HD void rollout_vjp_eval(const T *mdl, T (&qv)[N], T (&qdv)[N], T dt, int K, 
         }
         // (the reloaded state passes the check a second time: the same values, the same verdict)
         T cs[N], sn[N], H[N][N], Di[N], av[N], vb[N], ab[N], mu[N];
-        vjp_step_fd<T, N, FAST>(mdl, qv, qdv, [&](T (&tv)[N]) { load_tau(k, tv); }, cs, sn, H, Di, av, gd);
+        step(k, qv, qdv, cs, sn, H, Di, av, gd);
         {
             T gq[N], gqd[N];
             load_g(k, gq, gqd);
@@ -111,19 +116,37 @@ RB_HD void rollout_vjp_eval(const T *mdl, T (&qv)[N], T (&qdv)[N], T dt, int K, 
                 for (int i = 0; i < N; ++i) s = fmadd(-col[i], mu[i], s);
                 lv[c] = s;
             });
+        extra(qv, qdv, cs, sn, mu, lq, lv);
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) out_state(j, gd.out(lq[j]), gd.out(lv[j]));
 }
 
+// The contact-free rollout: load_tau(k, tv) step k's torques.
+template <typename T, int N, bool FAST, typename LoadTau, typename LoadG, typename WorkSt, typename WorkLd,
+          typename OutTau, typename OutState>
+RB_HD void rollout_vjp_eval(const T *mdl, T (&qv)[N], T (&qdv)[N], T dt, int K, LoadTau &&load_tau, LoadG &&load_g,
+                            WorkSt &&work_st, WorkLd &&work_ld, OutTau &&out_tau, OutState &&out_state) {
+    rollout_adjoint_eval<T, N>(
+        mdl, qv, qdv, dt, K,
+        [&](int k, const T (&q_)[N], const T (&v_)[N], T (&cs)[N], T (&sn)[N], T (&H)[N][N], T (&Di)[N], T (&av)[N],
+            InputGuard<T> &gd) {
+            vjp_step_fd<T, N, FAST>(mdl, q_, v_, [&](T (&tv)[N]) { load_tau(k, tv); }, cs, sn, H, Di, av, gd);
+        },
+        [](const T (&)[N], const T (&)[N], const T (&)[N], const T (&)[N], const T (&)[N], T (&)[N], T (&)[N]) {},
+        static_cast<LoadG &&>(load_g), static_cast<WorkSt &&>(work_st), static_cast<WorkLd &&>(work_ld),
+        static_cast<OutTau &&>(out_tau), static_cast<OutState &&>(out_state));
+}
+
 // Lane body (model-specialised kernels only, SoA rows; b: the configuration, b * sizeof(T) < 2^32).
 // q, qd, g_q0, g_qd0 [n][ld]; tau_seq, gq, gqd, g_tau [K][n][ld]; work [K][2n][ld].
-template <typename T, int N, bool FAST>
-__device__ __forceinline__ void rollout_vjp_lane(const T *mdl, const T *__restrict__ q, const T *__restrict__ qd,
-                                                 const T *__restrict__ tau_seq, T dt, int K,
-                                                 const T *__restrict__ gq, const T *__restrict__ gqd,
-                                                 T *__restrict__ g_q0, T *__restrict__ g_qd0, T *__restrict__ g_tau,
-                                                 T *work, uint32_t b, int64_t ld) {
+// eval(qv, qdv, load_tau, load_g, work_st, work_ld, out_tau, out_state): the sweeps on these rows.
+template <typename T, int N, typename Eval>
+__device__ __forceinline__ void rollout_adjoint_lane(const T *__restrict__ q, const T *__restrict__ qd,
+                                                     const T *__restrict__ tau_seq, const T *__restrict__ gq,
+                                                     const T *__restrict__ gqd, T *__restrict__ g_q0,
+                                                     T *__restrict__ g_qd0, T *__restrict__ g_tau, T *work, uint32_t b,
+                                                     int64_t ld, Eval &&eval) {
     const uint32_t off = b * (uint32_t)sizeof(T);
     T qv[N], qdv[N];
 #pragma unroll
@@ -131,8 +154,8 @@ __device__ __forceinline__ void rollout_vjp_lane(const T *mdl, const T *__restri
         qv[j] = ld_row(q, j * ld, off);
         qdv[j] = ld_row(qd, j * ld, off);
     }
-    rollout_vjp_eval<T, N, FAST>(
-        mdl, qv, qdv, dt, K,
+    eval(
+        qv, qdv,
         [&](int k, T (&tv)[N]) {
 #pragma unroll
             for (int j = 0; j < N; ++j) tv[j] = ld_row(tau_seq, ((int64_t)k * N + j) * ld, off);
@@ -151,6 +174,17 @@ __device__ __forceinline__ void rollout_vjp_lane(const T *mdl, const T *__restri
             st_row(g_q0, j * ld, off, a);
             st_row(g_qd0, j * ld, off, c);
         });
+}
+
+template <typename T, int N, bool FAST>
+__device__ __forceinline__ void rollout_vjp_lane(const T *mdl, const T *__restrict__ q, const T *__restrict__ qd,
+                                                 const T *__restrict__ tau_seq, T dt, int K,
+                                                 const T *__restrict__ gq, const T *__restrict__ gqd,
+                                                 T *__restrict__ g_q0, T *__restrict__ g_qd0, T *__restrict__ g_tau,
+                                                 T *work, uint32_t b, int64_t ld) {
+    rollout_adjoint_lane<T, N>(q, qd, tau_seq, gq, gqd, g_q0, g_qd0, g_tau, work, b, ld, [&](T (&qv)[N], T (&qdv)[N], auto &&...rows) {
+        rollout_vjp_eval<T, N, FAST>(mdl, qv, qdv, dt, K, static_cast<decltype(rows) &&>(rows)...);
+    });
 }
 
 }  // namespace dev

@@ -16,17 +16,20 @@ positions and a cost on it is written in torch:
 Scope: the gradient's (serial revolute chains on the mass-matrix forward dynamics, up to 12 links).
 For chains of 9 to 12 links the forward rollout integrates the articulated-body form and the
 gradient differentiates the mass-matrix form: the same function to rounding.
+
+`rollout_contact(mc, q0, qd0, tau_seq, dt)` is the same function of a handle that carries a contact
+set: Multibody.rollout_contact_batch forward, one Multibody.rollout_contact_vjp_batch launch backward.
 """
 import torch
 
 
 class _Rollout(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mb, q0, qd0, tau_seq, dt):
+    def forward(ctx, mb, q0, qd0, tau_seq, dt, contact=False):
         q, qd = q0.detach().clone(), qd0.detach().clone()
         tau = tau_seq.detach().contiguous()
-        traj = mb.rollout_batch(q, qd, tau, dt, traj=True)
-        ctx.mb, ctx.dt = mb, dt
+        traj = mb.rollout_contact_batch(q, qd, tau, dt) if contact else mb.rollout_batch(q, qd, tau, dt, traj=True)
+        ctx.mb, ctx.dt, ctx.contact = mb, dt, contact
         ctx.save_for_backward(q0.detach(), qd0.detach(), tau)
         return traj, qd
 
@@ -37,8 +40,9 @@ class _Rollout(torch.autograd.Function):
         gqd = torch.zeros_like(tau)
         if grad_qd_final is not None:
             gqd[-1] = grad_qd_final
-        g_q0, g_qd0, g_tau = ctx.mb.rollout_vjp_batch(q0.contiguous(), qd0.contiguous(), tau, ctx.dt, gq, gqd)
-        return None, g_q0, g_qd0, g_tau, None
+        vjp = ctx.mb.rollout_contact_vjp_batch if ctx.contact else ctx.mb.rollout_vjp_batch
+        g_q0, g_qd0, g_tau = vjp(q0.contiguous(), qd0.contiguous(), tau, ctx.dt, gq, gqd)
+        return None, g_q0, g_qd0, g_tau, None, None
 
 
 def rollout(mb, q0, qd0, tau_seq, dt):
@@ -49,3 +53,12 @@ def rollout(mb, q0, qd0, tau_seq, dt):
     if tau_seq.shape[0] < 1:
         raise ValueError("rollout needs at least one step (tau_seq [K, n, B], K >= 1)")
     return _Rollout.apply(mb, q0, qd0, tau_seq, float(dt))
+
+
+def rollout_contact(mb, q0, qd0, tau_seq, dt):
+    """rollout on a handle that carries a contact set (Multibody.with_contacts): the forward is one
+    Multibody.rollout_contact_batch launch, the backward one Multibody.rollout_contact_vjp_batch launch
+    (rigidbody_batch.h "reverse-mode gradient of the fused contact rollout"); the same values returned."""
+    if tau_seq.shape[0] < 1:
+        raise ValueError("rollout_contact needs at least one step (tau_seq [K, n, B], K >= 1)")
+    return _Rollout.apply(mb, q0, qd0, tau_seq, float(dt), True)

@@ -116,6 +116,9 @@ _SIGNATURES = {
     "multibody_rollout_contact": (_int, [_vp, _dp, _dp, _dp, _dbl, _int, _dp]),
     "multibody_contact_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
     "multibody_contact_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
+    "multibody_rollout_contact_vjp": (_int, [_vp, _dp, _dp, _dp, _dbl, _int] + [_dp] * 5),
+    "multibody_contact_vjp_jit_source": (_int, [_vp, _int, _i64, _str, _i64]),
+    "multibody_contact_vjp_jit_compile": (_i64, [_vp, _int, _i64, _str]),
 }
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
 _ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7,
@@ -133,6 +136,8 @@ for _t in ("f32", "f64"):
     # (handle, q, qd, tau_seq, dt, K, gq, gqd, g_q0, g_qd0, g_tau[, work], batch[, ld, stream])
     _SIGNATURES[f"multibody_rollout_vjp_batch_{_t}"] = (_int, [_vp] * 4 + [_dbl, _int] + [_vp] * 6 + [_i64, _i64, _vp])
     _SIGNATURES[f"multibody_rollout_vjp_batch_host_{_t}"] = (_int, [_vp] * 4 + [_dbl, _int] + [_vp] * 5 + [_i64])
+    for _k in ("batch", "batch_host"):
+        _SIGNATURES[f"multibody_rollout_contact_vjp_{_k}_{_t}"] = _SIGNATURES[f"multibody_rollout_vjp_{_k}_{_t}"]
     _SIGNATURES[f"rb_fill_uniform_{_t}"] = (_int, [_vp, _int, _i64, _i64, _dp, _dp, _u64, _vp])
     _SIGNATURES[f"rb_to_tiled_{_t}"] = (_int, [_vp, _i64, _vp, _int, _i64, _vp])
     _SIGNATURES[f"rb_from_tiled_{_t}"] = (_int, [_vp, _vp, _i64, _int, _i64, _vp])
@@ -431,7 +436,7 @@ class Multibody:
         _check(_lib.multibody_fd_deriv(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau, qdd, *outs)]), "fd_deriv")
         return (qdd, *(o.reshape(self.n, self.n).T.copy() for o in outs))
 
-    def rollout_vjp(self, q, qd, tau_seq, dt, gq, gqd):
+    def rollout_vjp(self, q, qd, tau_seq, dt, gq, gqd, _op="rollout_vjp"):
         """multibody_rollout_vjp: (g_q0 [n], g_qd0 [n], g_tau [K, n]), the gradient of
         sum_k gq[k] . q_{k+1} + gqd[k] . qd_{k+1} over the K-step rollout from (q, qd) under tau_seq
         [K, n]; gq, gqd [K, n].  One configuration, on the calling thread."""
@@ -442,25 +447,39 @@ class Multibody:
             if a.shape != (K, self.n):
                 raise ValueError(f"tau_seq, gq and gqd must all be [K, {self.n}], got {a.shape}")
         outs = [np.empty(self.n), np.empty(self.n), np.empty((K, self.n))]
-        _check(_lib.multibody_rollout_vjp(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau_seq)], float(dt), K,
-                                          *[a.ctypes.data_as(_dp) for a in (gq, gqd, *outs)]), "rollout_vjp")
+        _check(getattr(_lib, f"multibody_{_op}")(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, tau_seq)], float(dt), K,
+                                                 *[a.ctypes.data_as(_dp) for a in (gq, gqd, *outs)]), _op)
         return tuple(outs)
 
-    def rollout_vjp_jit_source(self, f64=False, batch=1 << 20) -> str:
+    def rollout_contact_vjp(self, q, qd, tau_seq, dt, gq, gqd):
+        """multibody_rollout_contact_vjp: rollout_vjp through the contact rollout of a handle that carries
+        a contact set (rollout_contact's trajectory on the mass-matrix forward dynamics)."""
+        return self.rollout_vjp(q, qd, tau_seq, dt, gq, gqd, _op="rollout_contact_vjp")
+
+    def rollout_vjp_jit_source(self, f64=False, batch=1 << 20, _op="rollout_vjp") -> str:
         """hipRTC source of the rollout gradient's kernel (multibody_rollout_vjp_jit_source); the
         empty string for a model outside its scope."""
-        n = _lib.multibody_rollout_vjp_jit_source(self._h, int(bool(f64)), int(batch), None, 0)
+        fn = getattr(_lib, f"multibody_{_op}_jit_source")
+        n = fn(self._h, int(bool(f64)), int(batch), None, 0)
         if n < 0:
             raise RigidBodyError(last_error())
         buf = ctypes.create_string_buffer(n + 1)
-        _lib.multibody_rollout_vjp_jit_source(self._h, int(bool(f64)), int(batch), buf, n + 1)
+        fn(self._h, int(bool(f64)), int(batch), buf, n + 1)
         return buf.value.decode()
 
-    def rollout_vjp_jit_compile(self, f64=False, arch="gfx950", batch=1 << 20) -> int:
-        r = _lib.multibody_rollout_vjp_jit_compile(self._h, int(bool(f64)), int(batch), arch.encode())
+    def rollout_vjp_jit_compile(self, f64=False, arch="gfx950", batch=1 << 20, _op="rollout_vjp") -> int:
+        r = getattr(_lib, f"multibody_{_op}_jit_compile")(self._h, int(bool(f64)), int(batch), arch.encode())
         if r < 0:
             raise RigidBodyError(last_error())
         return r
+
+    def contact_vjp_jit_source(self, f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the contact rollout gradient's kernel (multibody_contact_vjp_jit_source); the
+        empty string for a model outside its scope or without a contact set."""
+        return self.rollout_vjp_jit_source(f64, batch, _op="contact_vjp")
+
+    def contact_vjp_jit_compile(self, f64=False, arch="gfx950", batch=1 << 20) -> int:
+        return self.rollout_vjp_jit_compile(f64, arch, batch, _op="contact_vjp")
 
     # ---- external link wrenches: fext holds link j's force then its moment, in its URDF link frame
     def rnea_ext(self, q, qd, qdd, fext) -> np.ndarray:
@@ -930,7 +949,7 @@ class Multibody:
                    "rollout_batch")
         return tr
 
-    def rollout_vjp_batch(self, q, qd, tau_seq, dt, gq, gqd, stream=None):
+    def rollout_vjp_batch(self, q, qd, tau_seq, dt, gq, gqd, stream=None, _op="rollout_vjp"):
         """multibody_rollout_vjp_batch_*: the reverse-mode gradient of rollout_batch in one launch.
         q, qd [n, B] (the initial state, not modified), tau_seq [K, n, B]; gq, gqd [K, n, B] are the
         cotangents of the state after step k (gq[k] pairs with traj[k], gqd[K-1] with the final qd).
@@ -955,15 +974,20 @@ class Multibody:
         dev = _one_device((q, qd, tau_seq, gq, gqd))
         g_q0, g_qd0, g_tau = torch.empty_like(q), torch.empty_like(qd), torch.empty_like(tau_seq)
         work = torch.empty((K, 2 * self.n, B), dtype=q.dtype, device=dev)
-        fn = getattr(_lib, f"multibody_rollout_vjp_batch_{_TORCH_SUFFIX[q.dtype]}")
+        fn = getattr(_lib, f"multibody_{_op}_batch_{_TORCH_SUFFIX[q.dtype]}")
         with torch.cuda.device(dev):
             _check(fn(self._h, q.data_ptr(), qd.data_ptr(), tau_seq.data_ptr(), float(dt), int(K), gq.data_ptr(),
                       gqd.data_ptr(), g_q0.data_ptr(), g_qd0.data_ptr(), g_tau.data_ptr(), work.data_ptr(), B,
-                      max(ld, B, 1), _stream_ptr(stream, dev)), "rollout_vjp_batch")
+                      max(ld, B, 1), _stream_ptr(stream, dev)), f"{_op}_batch")
         return g_q0, g_qd0, g_tau
 
+    def rollout_contact_vjp_batch(self, q, qd, tau_seq, dt, gq, gqd, stream=None):
+        """multibody_rollout_contact_vjp_batch_*: rollout_vjp_batch through rollout_contact_batch -- the
+        reverse-mode gradient of the fused contact rollout in one launch, the same arrays."""
+        return self.rollout_vjp_batch(q, qd, tau_seq, dt, gq, gqd, stream, _op="rollout_contact_vjp")
+
     # -------------------------------------------------------- batched, host [n, B]
-    def rollout_vjp_batch_host(self, q, qd, tau_seq, dt, gq, gqd, dtype=np.float64):
+    def rollout_vjp_batch_host(self, q, qd, tau_seq, dt, gq, gqd, dtype=np.float64, _op="rollout_vjp"):
         """Blocking host form of rollout_vjp_batch on numpy arrays: q, qd [n, B]; tau_seq, gq, gqd
         [K, n, B].  Returns (g_q0, g_qd0 [n, B], g_tau [K, n, B])."""
         q, qd = _host_soa((q, qd), self.n, dtype)
@@ -974,10 +998,14 @@ class Multibody:
             if a.shape != (K, self.n, B):
                 raise ValueError(f"tau_seq, gq and gqd must all be [K, {self.n}, {B}], got {a.shape}")
         outs = [np.empty_like(q), np.empty_like(q), np.empty_like(seqs[0])]
-        fn = getattr(_lib, f"multibody_rollout_vjp_batch_host_{'f32' if q.dtype == np.float32 else 'f64'}")
+        fn = getattr(_lib, f"multibody_{_op}_batch_host_{'f32' if q.dtype == np.float32 else 'f64'}")
         _check(fn(self._h, q.ctypes.data, qd.ctypes.data, seqs[0].ctypes.data, float(dt), K,
-                  *[a.ctypes.data for a in (seqs[1], seqs[2], *outs)], B), "rollout_vjp_batch_host")
+                  *[a.ctypes.data for a in (seqs[1], seqs[2], *outs)], B), f"{_op}_batch_host")
         return tuple(outs)
+
+    def rollout_contact_vjp_batch_host(self, q, qd, tau_seq, dt, gq, gqd, dtype=np.float64):
+        """Blocking host form of rollout_contact_vjp_batch on numpy arrays, as rollout_vjp_batch_host."""
+        return self.rollout_vjp_batch_host(q, qd, tau_seq, dt, gq, gqd, dtype, _op="rollout_contact_vjp")
 
     def _host_call(self, kind, ins, out_rows, dtype):
         """multibody_<kind>_batch_host_f64 / _f32 (blocking): `ins` as [n, B] numpy arrays of
