@@ -587,6 +587,103 @@ int multibody_link_vel(const Multibody *mb, const double *q, const double *qd, d
 int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_link_kin_jit_compile(const Multibody *mb, int vel, int f64, int64_t batch, const char *arch);
 
+/* ---- centre of mass, centroidal momentum, energy ---------------------------------- */
+/* The whole-body quantities costs and constraints of legged robots are written in, reduced on chip:
+ * 3 - 11 rows per configuration (6 n for the momentum matrix) instead of the 18 n rows of
+ * multibody_link_pose / _vel and a reduction in the caller's code.
+ *
+ * Definitions.  pos_j, R_j, lin_j, ang_j are what multibody_link_pose / multibody_link_vel define
+ * (URDF link frame of link j); m_j, c_j, Ic_j the mass, the centre of mass in that frame and the
+ * rotational inertia about c_j in that frame's axes, all after fixed-joint merging;
+ * M = multibody_total_mass(mb); g = 9.81.
+ *   x_j   = pos_j + R_j c_j                          link COM, base frame
+ *   xd_j  = R_j (lin_j + ang_j x c_j)                its velocity, base frame
+ *   com   = (1/M) sum_j m_j x_j
+ *   l     = sum_j m_j xd_j                           linear momentum (= M d com/dt)
+ *   k     = sum_j [ R_j (Ic_j ang_j) + m_j (x_j - com) x xd_j ]   angular momentum about com, base axes
+ *   hg    = [ l ; k ]                                [lin; ang], the ABI's row order
+ *   T     = 1/2 sum_j ( m_j |xd_j|^2 + ang_j . Ic_j ang_j )       = 1/2 qd^T sym(H) qd, H of multibody_crba
+ *   U     = g M com_z                                so that dU/dq = rnea(q, 0, 0)
+ *   A_G(q): the 6 x n centroidal momentum matrix, hg = A_G(q) qd for every qd; rows 0..2 / M are
+ *           the COM Jacobian
+ * Gravity is the reference's +9.81 base acceleration along base z, as everywhere in this ABI.  The
+ * six virtual links of a floating base are massless and count like any other link.
+ *
+ * Layout (SoA rows of leading dimension ld, configuration b; q, qd are [n][ld]):
+ *   com    [3][ld]    com[c * ld + b]
+ *   hg     [6][ld]    rows 0..2 l, rows 3..5 k
+ *   energy [2][ld]    row 0 T, row 1 U
+ *   ag     [6 n][ld]  ag[e * ld + b], e = row + 6 * col (column-major, the order of multibody_jac)
+ * The single-configuration forms take com [3], hg [6], energy [2], ag [6 n].
+ *
+ * Algorithm (centroidal_body.hip.hpp).  com / centroidal: one root-to-leaf sweep, one configuration
+ * per lane, carrying the world pose (and link velocity) of the current link and of links with more
+ * than one child only; a link adds m_j x_j, its momentum about the base origin and its energy to
+ * accumulators and is forgotten; k is shifted to com once at the end.  cmm: the forward sweep leaves
+ * each link's joint axis, origin and ten inertial numbers about the base origin in base coordinates,
+ * a leaf-to-root sweep sums them into subtree composites, and column k -- the momentum of subtree k
+ * under the unit motion of joint k, shifted to com -- is stored as it completes.
+ *
+ * Scope: every model the link-kinematics kernels run -- serial chains under either reading and of
+ * every supported length, general axes, kinematic trees, prismatic joints, a floating base -- with
+ * M > 0 (else RB_ERR_UNSUPPORTED).  Model-specialised (hipRTC) kernels only, no kind number: with
+ * hipRTC disabled or failed RB_ERR_UNSUPPORTED with the log.  SoA rows only (no tiled form), batches
+ * split at 2^28 per launch.
+ *
+ * Checks, in order: handle (RB_ERR_NULL), batch >= 0, ld >= batch (RB_ERR_ARG), batch == 0 (RB_OK,
+ * nothing else looked at), a NULL array (RB_ERR_NULL; every array is required), an output passed as
+ * one of the inputs or as another output (RB_ERR_ARG), a model without mass (RB_ERR_UNSUPPORTED),
+ * then hipRTC.
+ *
+ * Input domain: as above: a configuration with a NaN / Inf in q or qd, or an angle past the bound,
+ * gets NaN in every element of every output; the others are unaffected.  Every input is checked
+ * before the configuration's first row is stored.
+ *
+ * Accuracy (tests/test_centroidal_host.py, tests/test_gpu_centroidal.py; reference
+ * tests/centroidal_ref.py: the definitions above evaluated with the 6x6 Featherstone model's joint
+ * transforms and link inertias, A_G column k as hg at qd = e_k).  fp64: every element of every output
+ * |d| <= 1e-9 (1 + |ref|); hg = A_G qd, T = 1/2 qd^T sym(H) qd with H of multibody_crba and
+ * U = g M com_z to 1e-12 scaled; A_G[0:3]^T (0, 0, g) = rnea(q, 0, 0) to 1e-9 scaled; a floating
+ * base's three translation columns of A_G are [M 1; 0] to 1e-12 scaled.  fp32 against the fp64
+ * kernel on the same fp32-rounded inputs, per configuration and output array:
+ * max|d| <= 1e-4 (1 + max|ref|).
+ * Measured (MI355X, B = 257): fp64 against the reference 1.4e-15 FR3 / 2.2e-14 16 links / 6.3e-15
+ * five links with general axes / 1.9e-15 the 9-joint tree / 1.2e-14 floating base (the largest is energy or
+ * hg each time, com 3.4e-16 at most); hg = A_G qd 2.0e-14 at most (floating base), T against crba 3.4e-15,
+ * the gravity identity 9.4e-14 (16 links), U bit for bit, the translation columns 9.9e-15; kernel against
+ * the host form 2.2e-15; fp32 1.2e-6 at most (general axes, energy).  Single-configuration forms on the
+ * host: 1.4e-15 FR3, 1.7e-14 at most (30 links). */
+int multibody_com_batch_f32(const Multibody *mb, const float *q, float *com, int64_t batch, int64_t ld, void *stream);
+int multibody_com_batch_f64(const Multibody *mb, const double *q, double *com, int64_t batch, int64_t ld,
+                            void *stream);
+int multibody_centroidal_batch_f32(const Multibody *mb, const float *q, const float *qd, float *com, float *hg,
+                                   float *energy, int64_t batch, int64_t ld, void *stream);
+int multibody_centroidal_batch_f64(const Multibody *mb, const double *q, const double *qd, double *com, double *hg,
+                                   double *energy, int64_t batch, int64_t ld, void *stream);
+int multibody_cmm_batch_f32(const Multibody *mb, const float *q, float *ag, int64_t batch, int64_t ld, void *stream);
+int multibody_cmm_batch_f64(const Multibody *mb, const double *q, double *ag, int64_t batch, int64_t ld,
+                            void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch). */
+int multibody_com_batch_host_f32(const Multibody *mb, const float *q, float *com, int64_t batch);
+int multibody_com_batch_host_f64(const Multibody *mb, const double *q, double *com, int64_t batch);
+int multibody_centroidal_batch_host_f32(const Multibody *mb, const float *q, const float *qd, float *com, float *hg,
+                                        float *energy, int64_t batch);
+int multibody_centroidal_batch_host_f64(const Multibody *mb, const double *q, const double *qd, double *com,
+                                        double *hg, double *energy, int64_t batch);
+int multibody_cmm_batch_host_f32(const Multibody *mb, const float *q, float *ag, int64_t batch);
+int multibody_cmm_batch_host_f64(const Multibody *mb, const double *q, double *ag, int64_t batch);
+/* One configuration, fp64, caller-provided outputs, on the calling thread: the same lane body
+ * compiled for the host, no GPU needed.  The scope of multibody_link_pose: serial revolute chains of
+ * a multibody_supported_dofs length on an FMA3 / AVX2 CPU; anything else RB_ERR_UNSUPPORTED. */
+int multibody_com(const Multibody *mb, const double *q, double *com);
+int multibody_centroidal(const Multibody *mb, const double *q, const double *qd, double *com, double *hg,
+                         double *energy);
+int multibody_cmm(const Multibody *mb, const double *q, double *ag);
+/* Inspection of those kernels (no kind number): which = 0 com, 1 centroidal, 2 cmm (anything else
+ * RB_ERR_ARG); otherwise as multibody_link_kin_jit_source / _compile. */
+int multibody_centroidal_jit_source(const Multibody *mb, int which, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_centroidal_jit_compile(const Multibody *mb, int which, int f64, int64_t batch, const char *arch);
+
 /* ---- compliant ground contact ---------------------------------------------------- */
 /* The step between the link kinematics and the external wrenches: a contact model that maps
  * (q, qd) to fext, and a fused K-step rollout that evaluates it on chip at every step and

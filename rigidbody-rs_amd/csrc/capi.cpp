@@ -323,6 +323,25 @@ hipError_t launch_link_vel(const Multibody *mb, const T *q, const T *qd, T *vel,
                       [&] { return no_generic(mb, "the link kinematics run"); });
 }
 
+// Whole-body quantities (centroidal_body.hip.hpp): model-specialised kernels only, SoA rows, every
+// model with a positive total mass; com has 3 rows, hg 6, energy 2, ag 6 n.
+template <typename T>
+hipError_t launch_com(const Multibody *mb, bool cmm, const T *q, T *out, uint32_t B, int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    void *args[] = {&q, &out, &B, &ld, &bs};
+    return launch_any(mb, cmm ? rbamd::JitKind::Cmm : rbamd::JitKind::Com, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the centroidal kernels run"); });
+}
+
+template <typename T>
+hipError_t launch_centroidal(const Multibody *mb, const T *q, const T *qd, T *com, T *hg, T *energy, uint32_t B,
+                             int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    void *args[] = {&q, &qd, &com, &hg, &energy, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::Centroidal, sizeof(T) == 8, B, false, s, args,
+                      [&] { return no_generic(mb, "the centroidal kernels run"); });
+}
+
 // Compliant ground contact (contact_body.hip.hpp): model-specialised kernels only, SoA rows, every
 // model that carries a contact set; fext has 6 n rows, cforce 3 P.
 template <typename T>
@@ -647,6 +666,43 @@ int link_vel_batch(const Multibody *mb, const T *q, const T *qd, T *vel, int64_t
     });
 }
 
+// The centroidal entry points' own argument checks: every array present, no output that is also an
+// input or another output, a model with mass.  which: 0 com, 1 centroidal, 2 cmm.
+rbamd::JitKind centroidal_kind(int which) {
+    return which == 0 ? rbamd::JitKind::Com : which == 1 ? rbamd::JitKind::Centroidal : rbamd::JitKind::Cmm;
+}
+const char *centroidal_name(int which) { return which == 0 ? "com" : which == 1 ? "centroidal" : "cmm"; }
+
+template <typename T>
+int centroidal_args_ok(const Multibody *mb, int which, std::initializer_list<const T *> in,
+                       std::initializer_list<const T *> out) {
+    for (const T *p : out)
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    return deriv_args_ok<T>(mb, centroidal_kind(which), centroidal_name(which), in, out);
+}
+
+// com (cmm = false, out [3]) / cmm (out [6 n])
+template <typename T>
+int com_batch(const Multibody *mb, bool cmm, const T *q, T *out, int64_t batch, int64_t ld, void *stream) {
+    auto args_ok = [&] { return centroidal_args_ok<T>(mb, cmm ? 2 : 0, {q}, {out}); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, cmm ? "cmm launch" : "com launch",
+                         [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_com<T>(mb, cmm, at(q, n), at(out, cmm ? 6 * n : 3), nb, ld, (hipStream_t)stream);
+    });
+}
+
+template <typename T>
+int centroidal_batch(const Multibody *mb, const T *q, const T *qd, T *com, T *hg, T *energy, int64_t batch, int64_t ld,
+                     void *stream) {
+    auto args_ok = [&] { return centroidal_args_ok<T>(mb, 1, {q, qd}, {com, hg, energy}); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "centroidal launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_centroidal<T>(mb, at(q, n), at(qd, n), at(com, 3), at(hg, 6), at(energy, 2), nb, ld,
+                                    (hipStream_t)stream);
+    });
+}
+
 // The contact entry points' own argument checks: every array present, no output (the rollout's
 // state included) that is also an input or another output, a model that carries a contact set.
 template <typename T>
@@ -915,6 +971,26 @@ int link_vel_host(const Multibody *mb, const T *q, const T *qd, T *vel, int64_t 
         mb, {q, qd}, {n, n}, {vel}, {6 * n}, 0, false, batch,
         [&] { return link_kin_args_ok<T>(mb, true, {q, qd}, {vel}); },
         [&](T **i, T **o, hipStream_t s) { return link_vel_batch<T>(mb, i[0], i[1], o[0], batch, batch, s); });
+}
+
+template <typename T>
+int com_host(const Multibody *mb, bool cmm, const T *q, T *out, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call_rows<T, 1, 1>(
+        mb, {q}, {n}, {out}, {cmm ? 6 * n : 3}, 0, false, batch,
+        [&] { return centroidal_args_ok<T>(mb, cmm ? 2 : 0, {q}, {out}); },
+        [&](T **i, T **o, hipStream_t s) { return com_batch<T>(mb, cmm, i[0], o[0], batch, batch, s); });
+}
+
+template <typename T>
+int centroidal_host(const Multibody *mb, const T *q, const T *qd, T *com, T *hg, T *energy, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    return host_call_rows<T, 2, 3>(
+        mb, {q, qd}, {n, n}, {com, hg, energy}, {3, 6, 2}, 0, false, batch,
+        [&] { return centroidal_args_ok<T>(mb, 1, {q, qd}, {com, hg, energy}); },
+        [&](T **i, T **o, hipStream_t s) {
+            return centroidal_batch<T>(mb, i[0], i[1], o[0], o[1], o[2], batch, batch, s);
+        });
 }
 
 template <typename T>
@@ -1239,6 +1315,15 @@ int ext_kind(int fd) { return (int)(fd ? rbamd::JitKind::FdExt : rbamd::JitKind:
 // ... nor the link-kinematics kernels (check_ext_query's checks): vel selects link_vel (else link_pose).
 int link_kin_kind(int vel) { return (int)(vel ? rbamd::JitKind::LinkVel : rbamd::JitKind::LinkPose); }
 
+// ... nor the centroidal kernels: which = 0 com, 1 centroidal, 2 cmm; a model without mass has none
+// (RB_ERR_UNSUPPORTED, the empty source).
+int check_centroidal_query(const Multibody *mb, int which, int64_t batch) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (which < 0 || which > 2) return set_err(RB_ERR_ARG, "which must be 0 com, 1 centroidal or 2 cmm");
+    if (batch < 1) return set_err(RB_ERR_ARG, "batch must be positive");
+    return deriv_supported(mb, centroidal_kind(which));
+}
+
 // ... nor the contact kernels: rollout selects rollout_contact (else contact_wrench); a model without
 // a contact set has neither (RB_ERR_UNSUPPORTED, the empty source).
 int contact_kind(int rollout) {
@@ -1331,6 +1416,15 @@ int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t
 int64_t multibody_link_kin_jit_compile(const Multibody *mb, int vel, int f64, int64_t batch, const char *arch) {
     if (int rc = check_ext_query(mb, batch)) return -rc;
     return compile_query(mb, link_kin_kind(vel), f64, batch, 0, arch);
+}
+
+int multibody_centroidal_jit_source(const Multibody *mb, int which, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_centroidal_query(mb, which, batch), (int)centroidal_kind(which), f64, batch, 0, buf, cap);
+}
+
+int64_t multibody_centroidal_jit_compile(const Multibody *mb, int which, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_centroidal_query(mb, which, batch)) return -rc;
+    return compile_query(mb, (int)centroidal_kind(which), f64, batch, 0, arch);
 }
 
 int multibody_contact_jit_source(const Multibody *mb, int rollout, int f64, int64_t batch, char *buf, int64_t cap) {
@@ -1749,6 +1843,83 @@ int multibody_link_pose(const Multibody *mb, const double *q, double *pos, doubl
 }
 int multibody_link_vel(const Multibody *mb, const double *q, const double *qd, double *vel) {
     return link_kin_single(mb, true, q, qd, vel, nullptr);
+}
+
+// ------------------------------------------------- centre of mass, centroidal momentum, energy
+int multibody_com_batch_f32(const Multibody *mb, const float *q, float *com, int64_t batch, int64_t ld, void *stream) {
+    return com_batch<float>(mb, false, q, com, batch, ld, stream);
+}
+int multibody_com_batch_f64(const Multibody *mb, const double *q, double *com, int64_t batch, int64_t ld,
+                            void *stream) {
+    return com_batch<double>(mb, false, q, com, batch, ld, stream);
+}
+int multibody_centroidal_batch_f32(const Multibody *mb, const float *q, const float *qd, float *com, float *hg,
+                                   float *energy, int64_t batch, int64_t ld, void *stream) {
+    return centroidal_batch<float>(mb, q, qd, com, hg, energy, batch, ld, stream);
+}
+int multibody_centroidal_batch_f64(const Multibody *mb, const double *q, const double *qd, double *com, double *hg,
+                                   double *energy, int64_t batch, int64_t ld, void *stream) {
+    return centroidal_batch<double>(mb, q, qd, com, hg, energy, batch, ld, stream);
+}
+int multibody_cmm_batch_f32(const Multibody *mb, const float *q, float *ag, int64_t batch, int64_t ld, void *stream) {
+    return com_batch<float>(mb, true, q, ag, batch, ld, stream);
+}
+int multibody_cmm_batch_f64(const Multibody *mb, const double *q, double *ag, int64_t batch, int64_t ld,
+                            void *stream) {
+    return com_batch<double>(mb, true, q, ag, batch, ld, stream);
+}
+int multibody_com_batch_host_f32(const Multibody *mb, const float *q, float *com, int64_t batch) {
+    return com_host<float>(mb, false, q, com, batch);
+}
+int multibody_com_batch_host_f64(const Multibody *mb, const double *q, double *com, int64_t batch) {
+    return com_host<double>(mb, false, q, com, batch);
+}
+int multibody_centroidal_batch_host_f32(const Multibody *mb, const float *q, const float *qd, float *com, float *hg,
+                                        float *energy, int64_t batch) {
+    return centroidal_host<float>(mb, q, qd, com, hg, energy, batch);
+}
+int multibody_centroidal_batch_host_f64(const Multibody *mb, const double *q, const double *qd, double *com,
+                                        double *hg, double *energy, int64_t batch) {
+    return centroidal_host<double>(mb, q, qd, com, hg, energy, batch);
+}
+int multibody_cmm_batch_host_f32(const Multibody *mb, const float *q, float *ag, int64_t batch) {
+    return com_host<float>(mb, true, q, ag, batch);
+}
+int multibody_cmm_batch_host_f64(const Multibody *mb, const double *q, double *ag, int64_t batch) {
+    return com_host<double>(mb, true, q, ag, batch);
+}
+
+// Single configuration, fp64, on the calling thread (host_eval.cpp): multibody_link_pose's scope.
+// which: 0 com (out0), 1 centroidal (out0 com, out1 hg, out2 energy), 2 cmm (out0).
+static int centroidal_single(const Multibody *mb, int which, const double *q, const double *qd, double *out0,
+                             double *out1, double *out2) {
+    const std::string op = centroidal_name(which);
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = which == 1 ? centroidal_args_ok<double>(mb, 1, {q, qd}, {out0, out1, out2})
+                            : centroidal_args_ok<double>(mb, which, {q}, {out0}))
+        return rc;
+    if (!mb->model.serial_revolute())
+        return set_err(RB_ERR_UNSUPPORTED, op + ": the single-configuration form evaluates serial revolute chains only "
+                                           "(kinematic trees, prismatic joints and a floating base take the batched "
+                                           "entry points)");
+    const double *pk = mb->pk64.data();
+    const bool ok = which == 0   ? rbamd::host_com(mb->model, pk, q, out0)
+                    : which == 1 ? rbamd::host_centroidal(mb->model, pk, q, qd, out0, out1, out2)
+                                 : rbamd::host_cmm(mb->model, pk, q, out0);
+    if (!ok)
+        return set_err(RB_ERR_UNSUPPORTED, op + ": the single-configuration form runs on the host and needs an FMA3 / "
+                                           "AVX2 CPU");
+    return RB_OK;
+}
+int multibody_com(const Multibody *mb, const double *q, double *com) {
+    return centroidal_single(mb, 0, q, nullptr, com, nullptr, nullptr);
+}
+int multibody_centroidal(const Multibody *mb, const double *q, const double *qd, double *com, double *hg,
+                         double *energy) {
+    return centroidal_single(mb, 1, q, qd, com, hg, energy);
+}
+int multibody_cmm(const Multibody *mb, const double *q, double *ag) {
+    return centroidal_single(mb, 2, q, nullptr, ag, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------- compliant ground contact

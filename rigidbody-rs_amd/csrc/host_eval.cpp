@@ -18,6 +18,7 @@
 #include "rollout_vjp_body.hip.hpp"  // first: rnea_deriv_body declares the host reciprocal fdh_body's L D L^T takes
 #include "crba_body.hip.hpp"
 #include "dofs.hpp"
+#include "centroidal_body.hip.hpp"
 #include "contact_body.hip.hpp"
 #include "contact_vjp_body.hip.hpp"
 #include "ext_body.hip.hpp"
@@ -339,6 +340,33 @@ RB_HOST_FMA bool link_vel_fma(int n, const double *mdl, const double *ra, const 
     }
 }
 
+// which: 0 com (out0), 1 centroidal (out0 com, out1 hg, out2 energy), 2 cmm (out0)
+RB_HOST_FMA bool centroidal_fma(int n, int which, const double *mdl, const double *q, const double *qd, double *out0,
+                                double *out1, double *out2) {
+    switch (n) {
+#define X(N)                                                                                        \
+    case N: {                                                                                       \
+        double a[N], b[N];                                                                          \
+        for (int j = 0; j < N; ++j) {                                                               \
+            a[j] = q[j];                                                                            \
+            b[j] = qd ? qd[j] : 0.0;                                                                \
+        }                                                                                           \
+        auto o0 = [&](int e, double v) { out0[e] = v; };                                            \
+        if (which == 0)                                                                             \
+            dev::com_eval<double, N, false, HostSerialTopo<N>>(mdl, a, o0);                         \
+        else if (which == 2)                                                                        \
+            dev::cmm_eval<double, N, false, HostSerialTopo<N>>(mdl, a, o0);                         \
+        else                                                                                        \
+            dev::centroidal_eval<double, N, false, HostSerialTopo<N>>(                              \
+                mdl, a, b, o0, [&](int e, double v) { out1[e] = v; }, [&](int e, double v) { out2[e] = v; }); \
+        return true;                                                                                \
+    }
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 RB_HOST_FMA bool contact_wrench_fma(int n, const ContactSet &cs, const double *mdl, const double *ra, const double *q,
                                     const double *qd, double *fext, double *cforce) {
     switch (n) {
@@ -461,6 +489,19 @@ bool host_link_pose(const Model &m, const double *pk, const double *ra, const do
 bool host_link_vel(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                    double *vel) {
     return host_eval_supported(m) && link_vel_fma(m.n, pk, ra, q, qd, vel);
+}
+
+bool host_com(const Model &m, const double *pk, const double *q, double *com) {
+    return host_eval_supported(m) && centroidal_fma(m.n, 0, pk, q, nullptr, com, nullptr, nullptr);
+}
+
+bool host_centroidal(const Model &m, const double *pk, const double *q, const double *qd, double *com, double *hg,
+                     double *energy) {
+    return host_eval_supported(m) && centroidal_fma(m.n, 1, pk, q, qd, com, hg, energy);
+}
+
+bool host_cmm(const Model &m, const double *pk, const double *q, double *ag) {
+    return host_eval_supported(m) && centroidal_fma(m.n, 2, pk, q, nullptr, ag, nullptr, nullptr);
 }
 
 bool host_contact_wrench(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,

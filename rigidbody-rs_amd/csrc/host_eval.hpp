@@ -49,6 +49,13 @@ bool host_link_pose(const Model &m, const double *pk, const double *ra, const do
 bool host_link_vel(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                    double *vel);
 
+// Whole-body quantities (centroidal_body.hip.hpp): com [3]; hg [6] ([lin; ang] about com) and energy
+// [2] (T, U); ag [6 n], the centroidal momentum matrix, element row + 6 col.
+bool host_com(const Model &m, const double *pk, const double *q, double *com);
+bool host_centroidal(const Model &m, const double *pk, const double *q, const double *qd, double *com, double *hg,
+                     double *energy);
+bool host_cmm(const Model &m, const double *pk, const double *q, double *ag);
+
 // Compliant ground contact (contact_body.hip.hpp) of a model that carries a contact set: fext [6 n]
 // and cforce [3 P] of one configuration; K steps of the fused rollout (q, qd overwritten with the
 // final state, traj [K n]) on the forward-dynamics form host_fd_ext takes.

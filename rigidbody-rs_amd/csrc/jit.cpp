@@ -51,7 +51,8 @@ int jit_nt(JitKind kind) {
     if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt ||
         kind == JitKind::RolloutContact)
         return tuning().fd_nt & 3;
-    // CRBA, fwd_kin, jac, link_pose / link_vel and contact_wrench (output-bound, as jac)
+    // CRBA, fwd_kin, jac, link_pose / link_vel, contact_wrench and cmm (output-bound, as jac)
+    if (kind == JitKind::Com || kind == JitKind::Centroidal) return tuning().kin_nt >= 0 ? tuning().kin_nt & 3 : 3;  // as fwd_kin
     const int v = tuning().kin_nt;
     if (v >= 0) return v & 3;
     return kind == JitKind::FwdKin ? 3 : 2;  // 7 rows in / 3 out: non-temporal loads pay too
@@ -149,6 +150,9 @@ std::string jit_kind_unsupported(const Model &m, JitKind kind) {
     if (kind == JitKind::ContactWrench || kind == JitKind::RolloutContact)
         return m.contacts.n_points > 0 ? "" : std::string(kind == JitKind::ContactWrench ? "contact_wrench" : "rollout_contact") +
                ": the model carries no contact set (multibody_with_contacts makes a handle that does)";
+    if (kind == JitKind::Com || kind == JitKind::Centroidal || kind == JitKind::Cmm)
+        return m.total_mass() > 0 ? "" : std::string(kind == JitKind::Com ? "com" : kind == JitKind::Cmm ? "cmm" : "centroidal") +
+               ": the model has no mass (the centre of mass is undefined)";
     if (kind == JitKind::RolloutContactVjp && m.contacts.n_points < 1)
         return "rollout_contact_vjp: the model carries no contact set (multibody_with_contacts makes a handle that does)";
     if (kind != JitKind::RneaDeriv && kind != JitKind::FdDeriv && kind != JitKind::RolloutVjp &&
@@ -363,7 +367,9 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     // guard anchor below nine links, opaque constants, the fp64 4-wave target): each was adopted on an
     // A/B measurement of that kernel, none has been measured for this one.
     const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact || cvjp;
-    if ((deriv || vjp || contact) && !jit_kind_unsupported(m, kind).empty()) return "";
+    // centre of mass, centroidal momentum / energy, momentum matrix (centroidal_body.hip.hpp)
+    const bool cz = kind == JitKind::Com || kind == JitKind::Centroidal || kind == JitKind::Cmm;
+    if ((deriv || vjp || contact || cz) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
         double *c = &pk[(size_t)i * kLinkStride];
@@ -485,6 +491,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     }
     o << (cvjp                                              ? "#include \"contact_vjp_body.hip.hpp\"\n"
           : contact                                         ? "#include \"contact_body.hip.hpp\"\n"
+          : cz                                              ? "#include \"centroidal_body.hip.hpp\"\n"
           : lk                                              ? "#include \"link_kin_body.hip.hpp\"\n"
           : ext                                             ? "#include \"ext_body.hip.hpp\"\n"
           : vjp                                            ? "#include \"rollout_vjp_body.hip.hpp\"\n"
@@ -705,6 +712,20 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
             sig("const T *__restrict__ q, T *__restrict__ pos, T *__restrict__ rot, uint32_t B, int64_t ld, int64_t bs");
             o << lane_prologue << "  rbamd::dev::link_pose_lane<T, N, " << F
               << ", Topo>(kModel, kExtRa, q + o, pos + o, rot + o, threadIdx.x, ld);\n}\n";
+        }
+    } else if (cz) {
+        // one configuration per lane on SoA rows: com [3][ld], hg [6][ld], energy [2][ld], ag [6 N][ld]
+        if (kind == JitKind::Centroidal) {
+            sig("const T *__restrict__ q, const T *__restrict__ qd, T *__restrict__ com, T *__restrict__ hg, "
+                "T *__restrict__ energy, uint32_t B, int64_t ld, int64_t bs");
+            o << lane_prologue << "  rbamd::dev::centroidal_lane<T, N, " << F
+              << ", Topo>(kModel, q + o, qd + o, com + o, hg + o, energy + o, threadIdx.x, ld);\n}\n";
+        } else {
+            const bool cmm = kind == JitKind::Cmm;
+            sig(std::string("const T *__restrict__ q, T *__restrict__ ") + (cmm ? "ag" : "com") +
+                ", uint32_t B, int64_t ld, int64_t bs");
+            o << lane_prologue << "  rbamd::dev::" << (cmm ? "cmm_lane" : "com_lane") << "<T, N, " << F
+              << ", Topo>(kModel, q + o, " << (cmm ? "ag" : "com") << " + o, threadIdx.x, ld);\n}\n";
         }
     } else if (deriv) {
         // one configuration per lane on SoA rows; a NULL output is neither evaluated nor stored

@@ -47,16 +47,20 @@ namespace rbamd {
 // RolloutContactVjp: the reverse-mode gradient of the contact rollout (contact_vjp_body.hip.hpp):
 // RolloutVjp's scope on a model that carries a contact set, the set compiled in and part of jit_key.
 // Internal too: multibody_contact_vjp_jit_source / _compile.
+// Com / Centroidal / Cmm: centre of mass, centroidal momentum and energy, and the centroidal momentum
+// matrix (centroidal_body.hip.hpp), every model with a positive total mass, hipRTC only, one
+// configuration per lane on SoA rows.  Internal too: multibody_centroidal_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
     RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13, ContactWrench = 14, RolloutContact = 15,
-    RolloutContactVjp = 16
+    RolloutContactVjp = 16, Com = 17, Centroidal = 18, Cmm = 19
 };
-constexpr int kJitKinds = 17;
+constexpr int kJitKinds = 20;
 constexpr int kJitPublicKinds = 9;
 
-// Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds and the
-// rollout's gradient are restricted here; jit_source returns an empty source for a model this refuses.
+// Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds, the
+// rollout's gradient, the contact kinds (a contact set) and the centroidal kinds (a positive total
+// mass) are restricted here; jit_source returns an empty source for a model this refuses.
 std::string jit_kind_unsupported(const Model &m, JitKind kind);
 
 // One compiled kernel of a model: with the model and the tuning knobs (jit_key), everything its

@@ -107,6 +107,13 @@ _SIGNATURES = {
     "multibody_link_vel": (_int, [_vp] + [_dp] * 3),
     "multibody_link_kin_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
     "multibody_link_kin_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
+    # centre of mass, centroidal momentum and energy, momentum matrix: one configuration (handle, q, com) /
+    # (handle, q, qd, com, hg, energy) / (handle, q, ag); inspection (handle, which, f64, batch, ...)
+    "multibody_com": (_int, [_vp] + [_dp] * 2),
+    "multibody_centroidal": (_int, [_vp] + [_dp] * 5),
+    "multibody_cmm": (_int, [_vp] + [_dp] * 2),
+    "multibody_centroidal_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
+    "multibody_centroidal_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
     # compliant ground contact: the handle that carries a set, its getter; one configuration
     # (handle, q, qd, fext, cforce) / (handle, q, qd, tau_seq, dt, K, traj); inspection (handle,
     # rollout, f64, batch, ...)
@@ -122,11 +129,12 @@ _SIGNATURES = {
 }
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
 _ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7,
-           "rnea_ext": 5, "fd_ext": 5, "link_pose": 3, "link_vel": 3, "contact_wrench": 4}
+           "rnea_ext": 5, "fd_ext": 5, "link_pose": 3, "link_vel": 3, "contact_wrench": 4, "com": 2, "centroidal": 5,
+           "cmm": 2}
 for _t in ("f32", "f64"):
     for _k, _n in _ARRAYS.items():
         _SIGNATURES[f"multibody_{_k}_batch_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _i64, _vp])
-        if not _k.endswith(("_deriv", "_ext")) and not _k.startswith(("link_", "contact_")):
+        if not _k.endswith(("_deriv", "_ext")) and not _k.startswith(("link_", "contact_", "com", "centroidal", "cmm")):
             _SIGNATURES[f"multibody_{_k}_batch_tiled_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _vp])
         if _k not in ("crba", "fwd_kin", "jac"):
             _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
@@ -645,6 +653,85 @@ class Multibody:
     def link_vel_batch_host(self, q, qd, dtype=np.float64):
         """Blocking host form of link_vel_batch on numpy arrays."""
         return self._link_kin_host("link_vel", (q, qd), (6,), dtype)[0]
+
+    # ---- centre of mass, centroidal momentum, energy (rigidbody_batch.h has the definitions)
+    CENTROIDAL_KERNELS = {"com": 0, "centroidal": 1, "cmm": 2}
+
+    def com(self, q) -> np.ndarray:
+        """multibody_com: the centre of mass [3] in the base frame; one configuration, on the calling thread."""
+        q, out = _dvec(q, self.n), np.empty(3)
+        _check(_lib.multibody_com(self._h, q.ctypes.data_as(_dp), out.ctypes.data_as(_dp)), "com")
+        return out
+
+    def centroidal(self, q, qd):
+        """multibody_centroidal: (com [3], hg [6], energy [2]) of one configuration: hg the linear momentum,
+        then the angular momentum about com, base axes; energy (kinetic, potential = g M com_z)."""
+        q, qd = _dvec(q, self.n), _dvec(qd, self.n)
+        outs = [np.empty(3), np.empty(6), np.empty(2)]
+        _check(_lib.multibody_centroidal(self._h, *[a.ctypes.data_as(_dp) for a in (q, qd, *outs)]), "centroidal")
+        return tuple(outs)
+
+    def cmm_raw(self, q) -> np.ndarray:
+        """6 n column-major buffer exactly as multibody_cmm fills it."""
+        q, out = _dvec(q, self.n), np.empty(6 * self.n)
+        _check(_lib.multibody_cmm(self._h, q.ctypes.data_as(_dp), out.ctypes.data_as(_dp)), "cmm")
+        return out
+
+    def cmm(self, q) -> np.ndarray:
+        """multibody_cmm: the centroidal momentum matrix A_G (6, n), hg = A_G qd."""
+        return self.cmm_raw(q).reshape(self.n, 6).T.copy()
+
+    def centroidal_jit_source(self, which="centroidal", f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the "com" / "centroidal" / "cmm" kernel (or 0 / 1 / 2;
+        multibody_centroidal_jit_source)."""
+        a = (self._h, int(self.CENTROIDAL_KERNELS.get(which, which)), int(bool(f64)), int(batch))
+        n = _lib.multibody_centroidal_jit_source(*a, None, 0)
+        if n < 0:
+            raise RigidBodyError(last_error())
+        buf = ctypes.create_string_buffer(n + 1)
+        _lib.multibody_centroidal_jit_source(*a, buf, n + 1)
+        return buf.value.decode()
+
+    def centroidal_jit_compile(self, which="centroidal", f64=False, arch="gfx950", batch=1 << 20) -> int:
+        r = _lib.multibody_centroidal_jit_compile(self._h, int(self.CENTROIDAL_KERNELS.get(which, which)),
+                                                  int(bool(f64)), int(batch), arch.encode())
+        if r < 0:
+            raise RigidBodyError(last_error())
+        return r
+
+    def com_batch(self, q, out=None, stream=None):
+        """multibody_com_batch_*: q [n, B] -> com [3, B], base frame."""
+        return self._soa_call("com", [(q, "q")], [(out, "com", 3)], stream)[0]
+
+    def centroidal_batch(self, q, qd, com=None, hg=None, energy=None, stream=None):
+        """multibody_centroidal_batch_*: q, qd [n, B] -> (com [3, B], hg [6, B], energy [2, B]): rows 0..2 of
+        hg the linear momentum, 3..5 the angular momentum about com; energy row 0 T, row 1 U."""
+        return tuple(self._soa_call("centroidal", [(q, "q"), (qd, "qd")],
+                                    [(com, "com", 3), (hg, "hg", 6), (energy, "energy", 2)], stream))
+
+    def cmm_batch(self, q, out=None, stream=None):
+        """multibody_cmm_batch_*: q [n, B] -> ag [6 n, B], row r + 6 k: element (r, k) of A_G."""
+        return self._soa_call("cmm", [(q, "q")], [(out, "ag", 6 * self.n)], stream)[0]
+
+    def _centroidal_host(self, kind, ins, rows, dtype):
+        arrs = _host_soa(ins, self.n, dtype)
+        B = arrs[0].shape[1]
+        outs = [np.empty((r, B), dtype=arrs[0].dtype) for r in rows]
+        fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in (*arrs, *outs)], B), f"{kind}_batch_host")
+        return outs
+
+    def com_batch_host(self, q, dtype=np.float64):
+        """Blocking host form of com_batch on numpy arrays."""
+        return self._centroidal_host("com", (q,), (3,), dtype)[0]
+
+    def centroidal_batch_host(self, q, qd, dtype=np.float64):
+        """Blocking host form of centroidal_batch on numpy arrays -> (com, hg, energy)."""
+        return tuple(self._centroidal_host("centroidal", (q, qd), (3, 6, 2), dtype))
+
+    def cmm_batch_host(self, q, dtype=np.float64):
+        """Blocking host form of cmm_batch on numpy arrays."""
+        return self._centroidal_host("cmm", (q,), (6 * self.n,), dtype)[0]
 
     # ---- compliant ground contact (rigidbody_batch.h "compliant ground contact")
     def with_contacts(self, links, points, normal=(0.0, 0.0, 1.0), offset=0.0, stiffness=2000.0, damping=0.5,
