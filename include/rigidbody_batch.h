@@ -884,6 +884,107 @@ int multibody_rollout_contact_vjp(const Multibody *mb, const double *q, const do
 int multibody_contact_vjp_jit_source(const Multibody *mb, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_contact_vjp_jit_compile(const Multibody *mb, int f64, int64_t batch, const char *arch);
 
+/* ---- reverse-mode gradient of the inverse dynamics --------------------------------- */
+/* The gradient of a scalar cost of tau = rnea_ext(q, qd, qdd, fext) with respect to all four inputs,
+ * for every model multibody_rnea_ext_* runs on -- the first derivative in this ABI that works on
+ * kinematic trees, prismatic joints and a floating base.  One O(n) reverse sweep of the RNEA: it
+ * reads 4 n + 6 n rows and writes 3 n + 6 n, where multibody_rnea_deriv_* writes 2 n^2.
+ *
+ * Definition, for one configuration and the cotangent w [n] of tau:
+ *   L      = sum_i w_i tau_i
+ *   g_q    [n]     g_q[k]   = sum_i w_i d tau_i / d q_k
+ *   g_qd   [n]     g_qd[k]  = sum_i w_i d tau_i / d qd_k
+ *   g_qdd  [n]     = sym(H(q)) w           (the RNEA is affine in qdd with slope H, multibody_crba's)
+ *   g_fext [6 n]   g_fext_j = -J_j(q) w    (rows [lin; rot], link j's URDF link frame: minus what
+ *                                           multibody_link_vel(q, w) returns for link j)
+ * Frames, row orders and the gravity convention are those of multibody_rnea_ext_* and
+ * multibody_link_vel_*.  No Jacobian matrix is formed or stored.
+ *
+ * Layout: SoA rows of leading dimension ld; q, qd, qdd, w, g_q, g_qd, g_qdd [n][ld]; fext, g_fext
+ * [6 n][ld] as multibody_rnea_ext takes fext.
+ *
+ * Two families, every array required in both (the contract of every batched entry point here):
+ *   multibody_rnea_vjp_batch_*        tau = rnea_ext(q, qd, qdd, fext); also returns g_fext
+ *   multibody_rnea_vjp_plain_batch_*  tau = rnea(q, qd, qdd): a kernel variant that has no wrench rows
+ * The single-configuration multibody_rnea_vjp serves both: fext == NULL selects the plain RNEA (g_fext
+ * must then be NULL too, else RB_ERR_ARG), and with fext given g_fext may still be NULL (not evaluated).
+ *
+ * Checks, in order: handle (RB_ERR_NULL), batch >= 0, ld >= batch (RB_ERR_ARG), batch == 0 (RB_OK,
+ * nothing else looked at), a NULL array (RB_ERR_NULL), the single form's g_fext without fext
+ * (RB_ERR_ARG), an output that is also an input or is passed twice (RB_ERR_ARG), then hipRTC.
+ *
+ * Scope: every model the external-wrench kernels run -- serial chains under either reading and of
+ * every supported length, general axes, kinematic trees, prismatic joints, a floating base.
+ * Model-specialised (hipRTC) kernels only, no kind number: with hipRTC disabled or failed
+ * RB_ERR_UNSUPPORTED with the log.  One configuration per lane, SoA rows only, batches split at 2^28.
+ * The single-configuration form has the scope of multibody_rnea_ext.
+ *
+ * Input domain: q, qd, qdd and fext are checked as in multibody_rnea_ext_*: a configuration with a
+ * NaN / Inf input or an angle past the bound gets NaN in every element of every output, the others
+ * are unaffected; every input is checked before the configuration's first store.  The cotangent w is
+ * NOT checked (a NaN there propagates by arithmetic), as gq / gqd of multibody_rollout_vjp_*.
+ *
+ * Algorithm (rnea_vjp_body.hip.hpp), in spatial notation (X_j parent -> child, x / x* the motion /
+ * force cross products, e_j the wrench).  Pass A, root to leaf, is the RNEA's forward sweep fused
+ * with phi_j = X_j phi_p + S_j w_j (phi_base = 0), the adjoint of the transmitted force: L = sum_j
+ * phi_j . f_j and g_fext_j = -phi_j.  Pass B, leaf to root, accumulates F_j (the RNEA's), A_j = I_j
+ * phi_j + children and V_j = -phi_j x* (I_j v_j) - I_j (v_j x phi_j) + qd_j (S_j x* A_j) + children,
+ * each handed up as X_j^T . , and reads off g_qdd_j = S_j . A_j, g_qd_j = S_j . V_j + A_j . (v_j x S_j),
+ * g_q_j = phi_j . (S_j x* F_j) - A_j . (S_j x X_j a_p) - V_j . (S_j x v_j).  Every output leaves in
+ * pass B, after the last wrench row has been checked.
+ *
+ * Accuracy (tests/test_rnea_vjp_host.py, tests/test_gpu_rnea_vjp.py; reference tests/rnea_vjp_ref.py:
+ * Richardson central differences, h = 1e-3, of w . (oracle rnea - J^T fext) along a direction scaled to
+ * the inputs' ranges).  fp64: |<g, d> - ref| <= 1e-7 (1 + |ref|) wherever the reference is
+ * self-consistent to 1e-8; g_qdd = sym(H) w with H of multibody_crba and g_fext = -link_vel(q, w) to
+ * 1e-9 scaled; g_q, g_qd against multibody_rnea_deriv contracted with w to 1e-8 scaled (serial
+ * chains).  The kernel agrees with the host form of the same lane body to 2.52e-14 relative (10x the
+ * measured 2.52e-15).  fp32 against the fp64 kernel on the same fp32-rounded inputs, per configuration
+ * and output array: max|d| <= 2e-5 (1 + max|ref|) -- 7x the measured maximum, 2.71e-6 (floating base).
+ * Measured (MI355X, B = 257, first 40 configurations differenced, all 40 qualify): fp64 against the
+ * reference 4.7e-11 FR3 / 4.9e-11 12 links with general axes / 3.6e-10 16 links / 1.2e-11 the 9-joint
+ * tree / 1.1e-10 floating base (the reference's own self-consistency is 1.2e-9 at most); g_qdd against
+ * crba 9.6e-16 at most, g_fext against link_vel bit for bit, g_q / g_qd against rnea_deriv 7.8e-16 at
+ * most; the plain kernel against the wrench kernel at fext = 0 bit for bit; fp32 8.4e-7 FR3 / 7.8e-7 the
+ * tree / 2.7e-6 floating base.  Single-configuration form on the host: 7.0e-11 at most against the
+ * reference (12 links), identities 1.6e-15 at most (30 links).
+ * Timing (tools/rnea_vjp_bench.py, MI355X, 2^20 configurations, HIP-graph replay, interleaved with its
+ * neighbours): FR3 fp64 wrench form 253.0 us (0.55 of HBM peak), plain 107.3 (0.48), beside rnea_ext 115.4
+ * and rnea_deriv plus the two products with w in torch 770.0; fp32 97.8 (0.71) / 42.2 (0.61) beside 52.3 and
+ * 394.9; floating base fp64 789.1 (0.35) / 296.7 (0.35) beside rnea_ext 543.8, fp32 271.1 / 102.1 beside
+ * 104.9.  FR3 uses no scratch; the floating base's fp64 wrench kernel spills. */
+int multibody_rnea_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                 const float *fext, const float *w, float *g_q, float *g_qd, float *g_qdd,
+                                 float *g_fext, int64_t batch, int64_t ld, void *stream);
+int multibody_rnea_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                 const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
+                                 double *g_fext, int64_t batch, int64_t ld, void *stream);
+int multibody_rnea_vjp_plain_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                       const float *w, float *g_q, float *g_qd, float *g_qdd, int64_t batch,
+                                       int64_t ld, void *stream);
+int multibody_rnea_vjp_plain_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                       const double *w, double *g_q, double *g_qd, double *g_qdd, int64_t batch,
+                                       int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch). */
+int multibody_rnea_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                      const float *fext, const float *w, float *g_q, float *g_qd, float *g_qdd,
+                                      float *g_fext, int64_t batch);
+int multibody_rnea_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                      const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
+                                      double *g_fext, int64_t batch);
+int multibody_rnea_vjp_plain_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                            const float *w, float *g_q, float *g_qd, float *g_qdd, int64_t batch);
+int multibody_rnea_vjp_plain_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                            const double *w, double *g_q, double *g_qd, double *g_qdd, int64_t batch);
+/* One configuration, fp64, caller-provided outputs, on the calling thread: the same lane body compiled
+ * for the host, no GPU needed.  fext and g_fext may be NULL as described above. */
+int multibody_rnea_vjp(const Multibody *mb, const double *q, const double *qd, const double *qdd, const double *fext,
+                       const double *w, double *g_q, double *g_qd, double *g_qdd, double *g_fext);
+/* Inspection of those kernels (no kind number): ext != 0 selects the wrench form, else the plain one;
+ * otherwise as multibody_ext_jit_source / _compile. */
+int multibody_rnea_vjp_jit_source(const Multibody *mb, int ext, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_rnea_vjp_jit_compile(const Multibody *mb, int ext, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

@@ -585,6 +585,60 @@ int ext_batch(const Multibody *mb, bool fd, const T *q, const T *qd, const T *th
     });
 }
 
+// The inverse dynamics' reverse-mode gradient (rnea_vjp_body.hip.hpp): model-specialised kernels only,
+// SoA rows, every model.  wrench = false: the plain RNEA's kernel, which has no wrench parameters (fext and
+// g_fext are not looked at).
+template <typename T>
+hipError_t launch_rnea_vjp(const Multibody *mb, bool wrench, const T *q, const T *qd, const T *qdd, const T *fext, const T *w,
+                           T *g_q, T *g_qd, T *g_qdd, T *g_fext, uint32_t B, int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    auto refuse = [&] { return no_generic(mb, "the inverse dynamics' gradient runs"); };
+    if (wrench) {
+        void *args[] = {&q, &qd, &qdd, &fext, &w, &g_q, &g_qd, &g_qdd, &g_fext, &B, &ld, &bs};
+        return launch_any(mb, rbamd::JitKind::RneaVjpExt, sizeof(T) == 8, B, false, s, args, refuse);
+    }
+    void *args[] = {&q, &qd, &qdd, &w, &g_q, &g_qd, &g_qdd, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::RneaVjp, sizeof(T) == 8, B, false, s, args, refuse);
+}
+
+// rnea_vjp's own argument checks: every array present, no output that is also an input or another
+// output.  wrench: the form with fext / g_fext (else both are NULL and not looked at).  optional: the
+// single-configuration form, where fext NULL selects the plain RNEA (g_fext must then be NULL too) and
+// g_fext alone may be NULL (not evaluated).
+template <typename T>
+int rnea_vjp_args_ok(bool wrench, bool optional, const T *q, const T *qd, const T *qdd, const T *fext, const T *w,
+                     const T *g_q, const T *g_qd, const T *g_qdd, const T *g_fext) {
+    for (const T *p : {q, qd, qdd, w, g_q, g_qd, g_qdd})
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    if (wrench && !optional && (!fext || !g_fext)) return set_err(RB_ERR_NULL, "NULL array");
+    if (g_fext && !fext) return set_err(RB_ERR_ARG, "rnea_vjp: g_fext without fext (the plain RNEA has no wrench)");
+    const T *out[] = {g_q, g_qd, g_qdd, g_fext};
+    for (int a = 0; a < 4; ++a) {
+        if (!out[a]) continue;
+        for (const T *i : {q, qd, qdd, fext, w})
+            if (out[a] == i) return set_err(RB_ERR_ARG, "rnea_vjp: an output array is also an input");
+        for (int b = 0; b < a; ++b)
+            if (out[a] == out[b]) return set_err(RB_ERR_ARG, "rnea_vjp: two outputs are the same array");
+    }
+    return RB_OK;
+}
+
+// wrench = false: multibody_rnea_vjp_plain_batch_* (fext, g_fext NULL)
+template <typename T>
+int rnea_vjp_batch(const Multibody *mb, bool wrench, const T *q, const T *qd, const T *qdd, const T *fext, const T *w,
+                   T *g_q, T *g_qd, T *g_qdd, T *g_fext, int64_t batch, int64_t ld, void *stream) {
+    if (!wrench) {  // the plain family has no wrench arrays: the kernel is chosen by the family alone
+        fext = nullptr;
+        g_fext = nullptr;
+    }
+    auto args_ok = [&] { return rnea_vjp_args_ok<T>(wrench, false, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "rnea_vjp launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_rnea_vjp<T>(mb, wrench, at(q, n), at(qd, n), at(qdd, n), at(fext, 6 * n), at(w, n), at(g_q, n),
+                                  at(g_qd, n), at(g_qdd, n), at(g_fext, 6 * n), nb, ld, (hipStream_t)stream);
+    });
+}
+
 // RB_ERR_UNSUPPORTED (with the condition that failed) when `kind` has no kernel for this model.
 int deriv_supported(const Multibody *mb, rbamd::JitKind kind) {
     const std::string why = rbamd::jit_kind_unsupported(mb->model, kind);
@@ -955,6 +1009,23 @@ int ext_host(const Multibody *mb, bool fd, const T *q, const T *qd, const T *thi
     });
 }
 
+// wrench = false: multibody_rnea_vjp_plain_batch_host_* (fext, g_fext NULL)
+template <typename T>
+int rnea_vjp_host(const Multibody *mb, bool wrench, const T *q, const T *qd, const T *qdd, const T *fext, const T *w,
+                  T *g_q, T *g_qd, T *g_qdd, T *g_fext, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    auto check = [&] { return rnea_vjp_args_ok<T>(wrench, false, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext); };
+    if (!wrench)
+        return host_call_rows<T, 4, 3>(mb, {q, qd, qdd, w}, {n, n, n, n}, {g_q, g_qd, g_qdd}, {n, n, n}, 0, false, batch,
+                                       check, [&](T **i, T **o, hipStream_t s) {
+            return rnea_vjp_batch<T>(mb, false, i[0], i[1], i[2], nullptr, i[3], o[0], o[1], o[2], nullptr, batch, batch, s);
+        });
+    return host_call_rows<T, 5, 4>(mb, {q, qd, qdd, fext, w}, {n, n, n, 6 * n, n}, {g_q, g_qd, g_qdd, g_fext},
+                                   {n, n, n, 6 * n}, 0, false, batch, check, [&](T **i, T **o, hipStream_t s) {
+        return rnea_vjp_batch<T>(mb, true, i[0], i[1], i[2], i[3], i[4], o[0], o[1], o[2], o[3], batch, batch, s);
+    });
+}
+
 template <typename T>
 int link_pose_host(const Multibody *mb, const T *q, T *pos, T *rot, int64_t batch) {
     const int64_t n = mb ? mb->model.n : 0;
@@ -1312,6 +1383,8 @@ int check_ext_query(const Multibody *mb, int64_t batch) {
     return RB_OK;
 }
 int ext_kind(int fd) { return (int)(fd ? rbamd::JitKind::FdExt : rbamd::JitKind::RneaExt); }
+// ... nor the inverse dynamics' gradient (check_ext_query's checks): ext selects the wrench form.
+int rnea_vjp_kind(int ext) { return (int)(ext ? rbamd::JitKind::RneaVjpExt : rbamd::JitKind::RneaVjp); }
 // ... nor the link-kinematics kernels (check_ext_query's checks): vel selects link_vel (else link_pose).
 int link_kin_kind(int vel) { return (int)(vel ? rbamd::JitKind::LinkVel : rbamd::JitKind::LinkPose); }
 
@@ -1407,6 +1480,15 @@ int multibody_ext_jit_source(const Multibody *mb, int fd, int f64, int64_t batch
 int64_t multibody_ext_jit_compile(const Multibody *mb, int fd, int f64, int64_t batch, const char *arch) {
     if (int rc = check_ext_query(mb, batch)) return -rc;
     return compile_query(mb, ext_kind(fd), f64, batch, 0, arch);
+}
+
+int multibody_rnea_vjp_jit_source(const Multibody *mb, int ext, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_ext_query(mb, batch), rnea_vjp_kind(ext), f64, batch, 0, buf, cap);
+}
+
+int64_t multibody_rnea_vjp_jit_compile(const Multibody *mb, int ext, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_ext_query(mb, batch)) return -rc;
+    return compile_query(mb, rnea_vjp_kind(ext), f64, batch, 0, arch);
 }
 
 int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t batch, char *buf, int64_t cap) {
@@ -1784,6 +1866,62 @@ int multibody_rnea_ext(const Multibody *mb, const double *q, const double *qd, c
 int multibody_fd_ext(const Multibody *mb, const double *q, const double *qd, const double *tau, const double *fext,
                      double *qdd) {
     return ext_single(mb, true, q, qd, tau, fext, qdd);
+}
+
+// ------------------------------------------- reverse-mode gradient of the inverse dynamics
+int multibody_rnea_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                 const float *fext, const float *w, float *g_q, float *g_qd, float *g_qdd,
+                                 float *g_fext, int64_t batch, int64_t ld, void *stream) {
+    return rnea_vjp_batch<float>(mb, true, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext, batch, ld, stream);
+}
+int multibody_rnea_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                      const float *fext, const float *w, float *g_q, float *g_qd, float *g_qdd,
+                                      float *g_fext, int64_t batch) {
+    return rnea_vjp_host<float>(mb, true, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext, batch);
+}
+int multibody_rnea_vjp_plain_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                       const float *w, float *g_q, float *g_qd, float *g_qdd, int64_t batch,
+                                       int64_t ld, void *stream) {
+    return rnea_vjp_batch<float>(mb, false, q, qd, qdd, nullptr, w, g_q, g_qd, g_qdd, nullptr, batch, ld, stream);
+}
+int multibody_rnea_vjp_plain_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *qdd,
+                                            const float *w, float *g_q, float *g_qd, float *g_qdd, int64_t batch) {
+    return rnea_vjp_host<float>(mb, false, q, qd, qdd, nullptr, w, g_q, g_qd, g_qdd, nullptr, batch);
+}
+int multibody_rnea_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                 const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
+                                 double *g_fext, int64_t batch, int64_t ld, void *stream) {
+    return rnea_vjp_batch<double>(mb, true, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext, batch, ld, stream);
+}
+int multibody_rnea_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                      const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
+                                      double *g_fext, int64_t batch) {
+    return rnea_vjp_host<double>(mb, true, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext, batch);
+}
+int multibody_rnea_vjp_plain_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                       const double *w, double *g_q, double *g_qd, double *g_qdd, int64_t batch,
+                                       int64_t ld, void *stream) {
+    return rnea_vjp_batch<double>(mb, false, q, qd, qdd, nullptr, w, g_q, g_qd, g_qdd, nullptr, batch, ld, stream);
+}
+int multibody_rnea_vjp_plain_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *qdd,
+                                            const double *w, double *g_q, double *g_qd, double *g_qdd,
+                                            int64_t batch) {
+    return rnea_vjp_host<double>(mb, false, q, qd, qdd, nullptr, w, g_q, g_qd, g_qdd, nullptr, batch);
+}
+
+// Single configuration, fp64, on the calling thread (host_eval.cpp): multibody_rnea_ext's scope.
+int multibody_rnea_vjp(const Multibody *mb, const double *q, const double *qd, const double *qdd, const double *fext,
+                       const double *w, double *g_q, double *g_qd, double *g_qdd, double *g_fext) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = rnea_vjp_args_ok<double>(true, true, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext)) return rc;
+    if (!mb->model.serial_revolute())
+        return set_err(RB_ERR_UNSUPPORTED, "rnea_vjp: the single-configuration form evaluates serial revolute chains only "
+                                           "(kinematic trees, prismatic joints and a floating base take the batched "
+                                           "entry points)");
+    if (!rbamd::host_rnea_vjp(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext))
+        return set_err(RB_ERR_UNSUPPORTED, "rnea_vjp: the single-configuration form runs on the host and needs an FMA3 / "
+                                           "AVX2 CPU");
+    return RB_OK;
 }
 
 // ------------------------------------------------------------- kinematics of every link

@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "link_kin_body.hip.hpp"
 #include "rnea_body.hip.hpp"
+#include "rnea_vjp_body.hip.hpp"
 
 namespace rbamd {
 namespace {
@@ -420,6 +421,43 @@ RB_HOST_FMA bool rollout_contact_fma(int n, const ContactSet &cs, const double *
     }
 }
 
+// fext NULL: the plain RNEA's gradient (g_fext unused); g_fext NULL: not evaluated.
+template <int N>
+RB_HOST_FMA bool rnea_vjp_fma_n(const double *mdl, const double *ra, const double *q, const double *qd,
+                                const double *qdd, const double *fext, const double *w, double *g_q, double *g_qd,
+                                double *g_qdd, double *g_fext) {
+    double a[N], b[N], c[N], d[N];
+    for (int j = 0; j < N; ++j) {
+        a[j] = q[j];
+        b[j] = qd[j];
+        c[j] = qdd[j];
+        d[j] = w[j];
+    }
+    auto fx = [&](int r) { return fext[r]; };
+    auto oq = [&](int j, double v) { g_q[j] = v; };
+    auto oqd = [&](int j, double v) { g_qd[j] = v; };
+    auto oqdd = [&](int j, double v) { g_qdd[j] = v; };
+    auto of = [&](int r, double v) { g_fext[r] = v; };
+    if (fext)
+        dev::rnea_vjp_eval<double, N, false, HostSerialTopo<N>, true>(mdl, ra, a, b, c, d, fx, g_fext != nullptr, oq, oqd,
+                                                                      oqdd, of);
+    else
+        dev::rnea_vjp_eval<double, N, false, HostSerialTopo<N>, false>(mdl, ra, a, b, c, d, fx, false, oq, oqd, oqdd, of);
+    return true;
+}
+
+RB_HOST_FMA bool rnea_vjp_fma(int n, const double *mdl, const double *ra, const double *q, const double *qd,
+                              const double *qdd, const double *fext, const double *w, double *g_q, double *g_qd,
+                              double *g_qdd, double *g_fext) {
+    switch (n) {
+#define X(N) \
+    case N: return rnea_vjp_fma_n<N>(mdl, ra, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext);
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -480,6 +518,12 @@ bool host_rnea_ext(const Model &m, const double *pk, const double *ra, const dou
 bool host_fd_ext(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
                  const double *tau, const double *fext, double *qdd) {
     return host_eval_supported(m) && fd_ext_fma(m.n, pk, ra, q, qd, tau, fext, qdd);
+}
+
+bool host_rnea_vjp(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                   const double *qdd, const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
+                   double *g_fext) {
+    return host_eval_supported(m) && rnea_vjp_fma(m.n, pk, ra, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext);
 }
 
 bool host_link_pose(const Model &m, const double *pk, const double *ra, const double *q, double *pos, double *rot) {

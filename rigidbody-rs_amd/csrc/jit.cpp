@@ -47,7 +47,8 @@ std::string literal(double x, bool f64) {
 
 int jit_nt(JitKind kind) {
     // (the external-wrench kinds follow their plain neighbours: every row is touched once)
-    if (kind == JitKind::Rnea || kind == JitKind::RneaExt) return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
+    if (kind == JitKind::Rnea || kind == JitKind::RneaExt || kind == JitKind::RneaVjp || kind == JitKind::RneaVjpExt)
+        return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
     if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt ||
         kind == JitKind::RolloutContact)
         return tuning().fd_nt & 3;
@@ -369,6 +370,8 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const bool contact = kind == JitKind::ContactWrench || kind == JitKind::RolloutContact || cvjp;
     // centre of mass, centroidal momentum / energy, momentum matrix (centroidal_body.hip.hpp)
     const bool cz = kind == JitKind::Com || kind == JitKind::Centroidal || kind == JitKind::Cmm;
+    // the inverse dynamics' reverse-mode gradient (rnea_vjp_body.hip.hpp), without / with wrench rows
+    const bool rvjp = kind == JitKind::RneaVjp || kind == JitKind::RneaVjpExt;
     if ((deriv || vjp || contact || cz) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
@@ -492,6 +495,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     o << (cvjp                                              ? "#include \"contact_vjp_body.hip.hpp\"\n"
           : contact                                         ? "#include \"contact_body.hip.hpp\"\n"
           : cz                                              ? "#include \"centroidal_body.hip.hpp\"\n"
+          : rvjp                                            ? "#include \"rnea_vjp_body.hip.hpp\"\n"
           : lk                                              ? "#include \"link_kin_body.hip.hpp\"\n"
           : ext                                             ? "#include \"ext_body.hip.hpp\"\n"
           : vjp                                            ? "#include \"rollout_vjp_body.hip.hpp\"\n"
@@ -533,7 +537,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         for (size_t k = 0; k < pk.size(); ++k) o << "  " << literal(pk[k], f64) << ",\n";
     }
     o << "};\n";
-    if (ext || lk || contact) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
+    if (ext || lk || contact || rvjp) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
         const std::vector<double> ra = m.axis_frames();
         o << "static __device__ constexpr T kExtRa[" << ra.size() << "] = {\n";
         for (size_t k = 0; k < ra.size(); ++k) o << "  " << literal(snap(ra[k]), f64) << ",\n";
@@ -689,6 +693,18 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         else
             o << "  rbamd::dev::rnea_ext_lane<T, N, " << F
               << ", Topo>(kModel, kExtRa, q + o, qd + o, qdd + o, fext + o, tau + o, threadIdx.x, ld);\n}\n";
+    } else if (rvjp) {
+        // one configuration per lane on SoA rows; the plain form has no wrench parameters at all, the
+        // wrench form takes fext and g_fext [6 N][ld]
+        const bool wr = kind == JitKind::RneaVjpExt;
+        sig(std::string("const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ qdd, ") +
+            (wr ? "const T *__restrict__ fext, " : "") +
+            "const T *__restrict__ w, T *__restrict__ g_q, T *__restrict__ g_qd, T *__restrict__ g_qdd, " +
+            (wr ? "T *__restrict__ g_fext, " : "") + "uint32_t B, int64_t ld, int64_t bs");
+        o << lane_prologue << "  rbamd::dev::rnea_vjp_lane<T, N, " << F << ", Topo, " << (wr ? "true" : "false")
+          << ">(kModel, kExtRa, q + o, qd + o, qdd + o, " << (wr ? "fext + o" : "nullptr")
+          << ", w + o, g_q + o, g_qd + o, g_qdd + o, " << (wr ? "g_fext + o" : "nullptr")
+          << ", threadIdx.x, ld);\n}\n";
     } else if (kind == JitKind::ContactWrench) {
         // one configuration per lane on SoA rows: fext [6 N][ld], cforce [3 P][ld]
         sig("const T *__restrict__ q, const T *__restrict__ qd, T *__restrict__ fext, T *__restrict__ cforce, "

@@ -50,12 +50,15 @@ namespace rbamd {
 // Com / Centroidal / Cmm: centre of mass, centroidal momentum and energy, and the centroidal momentum
 // matrix (centroidal_body.hip.hpp), every model with a positive total mass, hipRTC only, one
 // configuration per lane on SoA rows.  Internal too: multibody_centroidal_jit_source / _compile.
+// RneaVjp / RneaVjpExt: the reverse-mode gradient of the inverse dynamics without / with external link
+// wrenches (rnea_vjp_body.hip.hpp), every model, hipRTC only, one configuration per lane on SoA rows.
+// Internal too: multibody_rnea_vjp_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
     RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13, ContactWrench = 14, RolloutContact = 15,
-    RolloutContactVjp = 16, Com = 17, Centroidal = 18, Cmm = 19
+    RolloutContactVjp = 16, Com = 17, Centroidal = 18, Cmm = 19, RneaVjp = 20, RneaVjpExt = 21
 };
-constexpr int kJitKinds = 20;
+constexpr int kJitKinds = 22;
 constexpr int kJitPublicKinds = 9;
 
 // Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds, the

@@ -19,6 +19,15 @@ gradient differentiates the mass-matrix form: the same function to rounding.
 
 `rollout_contact(mc, q0, qd0, tau_seq, dt)` is the same function of a handle that carries a contact
 set: Multibody.rollout_contact_batch forward, one Multibody.rollout_contact_vjp_batch launch backward.
+
+`rnea(mb, q, qd, qdd, fext=None)` is the inverse dynamics tau [n, B] as a differentiable function of
+its tensor arguments, on every model (kinematic trees, prismatic joints, a floating base included):
+one Multibody.rnea_batch / rnea_ext_batch launch forward, one Multibody.rnea_vjp_batch launch backward
+(rigidbody_batch.h "reverse-mode gradient of the inverse dynamics").
+
+    tau = rnea(mb, q, qd, qdd, fext)                         # [n, B]; fext [6 n, B] or None
+    cost = (tau ** 2).sum()
+    cost.backward()                                          # q.grad, qd.grad, qdd.grad, fext.grad
 """
 import torch
 
@@ -62,3 +71,28 @@ def rollout_contact(mb, q0, qd0, tau_seq, dt):
     if tau_seq.shape[0] < 1:
         raise ValueError("rollout_contact needs at least one step (tau_seq [K, n, B], K >= 1)")
     return _Rollout.apply(mb, q0, qd0, tau_seq, float(dt), True)
+
+
+class _Rnea(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mb, q, qd, qdd, fext):
+        ins = [t.detach().contiguous() for t in (q, qd, qdd)]
+        f = None if fext is None else fext.detach().contiguous()
+        tau = mb.rnea_batch(*ins) if f is None else mb.rnea_ext_batch(*ins, f)
+        ctx.mb, ctx.ext = mb, f is not None
+        ctx.save_for_backward(*ins, *([f] if f is not None else []))
+        return tau
+
+    @staticmethod
+    def backward(ctx, grad_tau):
+        saved = ctx.saved_tensors
+        g = ctx.mb.rnea_vjp_batch(*saved[:3], grad_tau.contiguous(), fext=saved[3] if ctx.ext else None)
+        g = list(g) + ([] if ctx.ext else [None])
+        return (None, *[x if need else None for x, need in zip(g, ctx.needs_input_grad[1:])])
+
+
+def rnea(mb, q, qd, qdd, fext=None):
+    """tau = rnea_ext(q, qd, qdd, fext) [n, B] (fext=None: the plain RNEA) of CUDA tensors q, qd, qdd [n, B]
+    and fext [6 n, B], fp32 or fp64 (the inputs are not modified), differentiable with respect to every
+    tensor argument; an input without requires_grad gets None."""
+    return _Rnea.apply(mb, q, qd, qdd, fext)
