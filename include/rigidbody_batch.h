@@ -985,6 +985,117 @@ int multibody_rnea_vjp(const Multibody *mb, const double *q, const double *qd, c
 int multibody_rnea_vjp_jit_source(const Multibody *mb, int ext, int f64, int64_t batch, char *buf, int64_t cap);
 int64_t multibody_rnea_vjp_jit_compile(const Multibody *mb, int ext, int f64, int64_t batch, const char *arch);
 
+/* ---- reverse-mode gradient of the forward dynamics --------------------------------- */
+/* The gradient of a scalar cost of qdd = fd_ext(q, qd, tau, fext) with respect to all four inputs, for
+ * every model multibody_fd_ext_* runs on (multibody_fd_deriv_* stops at serial revolute chains of up to
+ * 12 links), from one launch that also returns qdd.  It reads 4 n + 6 n rows and writes 4 n + 6 n; no
+ * mass matrix leaves the kernel.
+ *
+ * Definition, for one configuration and the cotangent w [n] of qdd:
+ *   L      = sum_i w_i qdd_i
+ *   qdd    [n]     what multibody_fd_ext_batch_* returns for the same inputs, bit for bit
+ *   g_tau  [n]     = mu = sym(H(q))^-1 w   (H of multibody_crba)
+ *   g_q    [n]     = -(g_q  of multibody_rnea_vjp at (q, qd, qdd, fext) with the cotangent mu)
+ *   g_qd   [n]     = -(g_qd of the same)
+ *   g_fext [6 n]   g_fext_j = +J_j(q) mu   (rows [lin; rot], link j's URDF link frame: what
+ *                                           multibody_link_vel(q, mu) returns for link j)
+ * which follows from H dqdd + d rnea_ext(q, qd, qdd, fext) = dtau.  Frames, row orders and the gravity
+ * convention are those of multibody_fd_ext_* and multibody_rnea_vjp_*.
+ *
+ * Layout: SoA rows of leading dimension ld; q, qd, tau, w, qdd, g_q, g_qd, g_tau [n][ld]; fext, g_fext
+ * [6 n][ld] as multibody_fd_ext takes fext.
+ *
+ * Two families, every array required in both (the contract of every batched entry point here):
+ *   multibody_fd_vjp_batch_*        qdd = fd_ext(q, qd, tau, fext); also returns g_fext
+ *   multibody_fd_vjp_plain_batch_*  qdd = fd_ext(q, qd, tau, 0): a kernel variant that has no wrench rows
+ *                                   (the wrench family's results at fext = 0, bit for bit)
+ * The single-configuration multibody_fd_vjp serves both: fext == NULL selects the plain form (g_fext must
+ * then be NULL too, else RB_ERR_ARG), and with fext given g_fext may still be NULL (not evaluated).
+ *
+ * Checks, in order: handle (RB_ERR_NULL), batch >= 0, ld >= batch (RB_ERR_ARG), batch == 0 (RB_OK,
+ * nothing else looked at), a NULL array (RB_ERR_NULL), the single form's g_fext without fext
+ * (RB_ERR_ARG), an output that is also an input or is passed twice (RB_ERR_ARG), then hipRTC.
+ *
+ * Scope: every model multibody_fd_ext_batch_* runs -- serial chains under either reading and of every
+ * supported length, general axes, kinematic trees, prismatic joints, a floating base.
+ * Model-specialised (hipRTC) kernels only, no kind number: with hipRTC disabled or failed
+ * RB_ERR_UNSUPPORTED with the log.  One configuration per lane, SoA rows only, batches split at 2^28.
+ * The single-configuration form has the scope of multibody_rnea_vjp.
+ *
+ * Input domain: q, qd, tau and fext are checked as in multibody_fd_ext_*: a configuration with a NaN /
+ * Inf input or an angle past the bound gets NaN in every element of every output, the others are
+ * unaffected; every input is checked before the configuration's first store.  The cotangent w is NOT
+ * checked (a NaN there propagates by arithmetic).
+ *
+ * Algorithm (fd_vjp_body.hip.hpp), two stages per lane.  Stage 1 is the forward dynamics in the form
+ * multibody_fd_ext takes for the model, with a second right-hand side: the mass-matrix form (serial
+ * chains up to 12 links) factorises H once and solves L D L^T x = b for (tau - C) and for w; the
+ * articulated-body form (longer chains, trees, a floating base) carries a second bias force and a
+ * second u / D through its passes 2 and 3 on the same articulated inertias.  Stage 2 is the reverse
+ * sweep of multibody_rnea_vjp at (q, qd, qdd; mu), its outputs negated.  The wrench rows are fetched by
+ * the link step that consumes them in each stage: they are read twice and never held together.
+ *
+ * Accuracy (tests/test_fd_vjp_host.py, tests/test_gpu_fd_vjp.py; reference tests/fd_vjp_ref.py: Richardson
+ * central differences, h = 1e-3, of w . (oracle fd at tau + J^T fext) along a direction scaled to the
+ * inputs' ranges).  fp64: |<g, d> - ref| <= 1e-7 (1 + |ref|) wherever the reference is self-consistent
+ * to 1e-8; qdd = multibody_fd_ext, sym(H) g_tau = w with H of multibody_crba and g_fext = link_vel(q,
+ * g_tau) to 1e-9 scaled; g_q, g_qd, g_tau against multibody_fd_deriv contracted with w to 1e-8 scaled
+ * (serial chains up to 12 links).  Measured (MI355X, B = 257, first 40 configurations differenced):
+ * against the reference 8.1e-10 FR3 / 6.5e-10 12 links with general axes / 3.1e-9 16 links (39 of 40
+ * qualify) / 3.0e-11 the 9-joint tree / 2.0e-11 floating base; qdd against multibody_fd_ext_batch bit for
+ * bit; sym(H) g_tau against w 4.4e-13 at most (16 links); g_fext against link_vel bit for bit; the plain
+ * kernel against the wrench kernel at fext = 0 bit for bit.  Against -multibody_rnea_vjp_batch at (q, qd,
+ * qdd, g_tau, fext): g_qd and g_fext bit for bit, g_q within 2.86e-15 scaled (10x the measured 2.86e-16:
+ * that kernel forms the link forces about the link origin, this one about the centre of mass, as
+ * multibody_fd_ext does).  The kernel agrees with the host form of the same lane body to 2.53e-13
+ * (10x the measured 2.53e-14).  fp32 against the fp64 kernel on the same fp32-rounded inputs, per
+ * configuration and output array: max|d| <= 1.6e-4 (1 + max|ref|) -- about 7x the measured maximum,
+ * 2.22e-5 (FR3; the tree 1.8e-6, floating base 5.5e-6).  Single-configuration form on the host: 4.3e-9 at
+ * most against the reference (30 links, 19 of 20 qualify), identities 2.7e-12 at most (30 links),
+ * multibody_fd_deriv 5.0e-14 at most.
+ * Timing (tools/fd_vjp_bench.py, profiles/fd_vjp/fd_vjp_bench.json; MI355X, 2^20 configurations, HIP-graph
+ * replay, interleaved with its neighbours, median us): FR3 fp64 wrench form 378.2 (0.39 of HBM peak), plain
+ * 159.3 (0.37), beside fd_ext 110.9, rnea_vjp 261.2 and the unfused composition (fd_ext, crba, a batched solve
+ * in torch, rnea_vjp; timed eagerly) 4909.9; fp32 126.9 (0.58) / 72.5 (0.40) beside 53.1, 99.5 and 3632.7;
+ * floating base fp64 1707.7 (0.17) / 627.1 (0.19) beside fd_ext 522.3 and rnea_vjp 798.8, fp32 696.1 / 326.3
+ * beside 125.8 and 268.6.  So on FR3 one launch costs what fd_ext plus rnea_vjp cost and is 13x / 29x faster
+ * than the composition; on the floating base it is slower than those two launches together (one wave per
+ * SIMD at 494-512 registers).  Resources (profiles/fd_vjp/resources.json): FR3 and the tree use
+ * no scratch; every variant of the 30-link chain and the fp64 variants of the floating base spill. */
+int multibody_fd_vjp_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                               const float *fext, const float *w, float *qdd, float *g_q, float *g_qd, float *g_tau,
+                               float *g_fext, int64_t batch, int64_t ld, void *stream);
+int multibody_fd_vjp_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                               const double *fext, const double *w, double *qdd, double *g_q, double *g_qd,
+                               double *g_tau, double *g_fext, int64_t batch, int64_t ld, void *stream);
+int multibody_fd_vjp_plain_batch_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                     const float *w, float *qdd, float *g_q, float *g_qd, float *g_tau, int64_t batch,
+                                     int64_t ld, void *stream);
+int multibody_fd_vjp_plain_batch_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                     const double *w, double *qdd, double *g_q, double *g_qd, double *g_tau,
+                                     int64_t batch, int64_t ld, void *stream);
+/* Blocking host-pointer forms: contiguous host arrays (ld = batch). */
+int multibody_fd_vjp_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                    const float *fext, const float *w, float *qdd, float *g_q, float *g_qd,
+                                    float *g_tau, float *g_fext, int64_t batch);
+int multibody_fd_vjp_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                    const double *fext, const double *w, double *qdd, double *g_q, double *g_qd,
+                                    double *g_tau, double *g_fext, int64_t batch);
+int multibody_fd_vjp_plain_batch_host_f32(const Multibody *mb, const float *q, const float *qd, const float *tau,
+                                          const float *w, float *qdd, float *g_q, float *g_qd, float *g_tau,
+                                          int64_t batch);
+int multibody_fd_vjp_plain_batch_host_f64(const Multibody *mb, const double *q, const double *qd, const double *tau,
+                                          const double *w, double *qdd, double *g_q, double *g_qd, double *g_tau,
+                                          int64_t batch);
+/* One configuration, fp64, caller-provided outputs, on the calling thread: the same lane body compiled
+ * for the host, no GPU needed.  fext and g_fext may be NULL as described above. */
+int multibody_fd_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau, const double *fext,
+                     const double *w, double *qdd, double *g_q, double *g_qd, double *g_tau, double *g_fext);
+/* Inspection of those kernels (no kind number): ext != 0 selects the wrench form, else the plain one;
+ * otherwise as multibody_ext_jit_source / _compile. */
+int multibody_fd_vjp_jit_source(const Multibody *mb, int ext, int f64, int64_t batch, char *buf, int64_t cap);
+int64_t multibody_fd_vjp_jit_compile(const Multibody *mb, int ext, int f64, int64_t batch, const char *arch);
+
 /* ---- batched host-pointer entry points (blocking) ------------------------------ */
 int multibody_rnea_batch_host_f64(const Multibody *mb, const double *q, const double *qd,
                                   const double *qdd, double *tau, int64_t batch);

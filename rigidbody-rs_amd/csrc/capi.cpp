@@ -639,6 +639,57 @@ int rnea_vjp_batch(const Multibody *mb, bool wrench, const T *q, const T *qd, co
     });
 }
 
+// The forward dynamics' reverse-mode gradient (fd_vjp_body.hip.hpp): model-specialised kernels only, SoA
+// rows, every model.  wrench = false: the kernel without wrench parameters (fext and g_fext are not
+// looked at).
+template <typename T>
+hipError_t launch_fd_vjp(const Multibody *mb, bool wrench, const T *q, const T *qd, const T *tau, const T *fext, const T *w,
+                         T *qdd, T *g_q, T *g_qd, T *g_tau, T *g_fext, uint32_t B, int64_t ld, hipStream_t s) {
+    int64_t bs = 256;
+    auto refuse = [&] { return no_generic(mb, "the forward dynamics' gradient runs"); };
+    if (wrench) {
+        void *args[] = {&q, &qd, &tau, &fext, &w, &qdd, &g_q, &g_qd, &g_tau, &g_fext, &B, &ld, &bs};
+        return launch_any(mb, rbamd::JitKind::FdVjpExt, sizeof(T) == 8, B, false, s, args, refuse);
+    }
+    void *args[] = {&q, &qd, &tau, &w, &qdd, &g_q, &g_qd, &g_tau, &B, &ld, &bs};
+    return launch_any(mb, rbamd::JitKind::FdVjp, sizeof(T) == 8, B, false, s, args, refuse);
+}
+
+// fd_vjp's own argument checks, rnea_vjp_args_ok's with qdd among the outputs.
+template <typename T>
+int fd_vjp_args_ok(bool wrench, bool optional, const T *q, const T *qd, const T *tau, const T *fext, const T *w,
+                   const T *qdd, const T *g_q, const T *g_qd, const T *g_tau, const T *g_fext) {
+    for (const T *p : {q, qd, tau, w, qdd, g_q, g_qd, g_tau})
+        if (!p) return set_err(RB_ERR_NULL, "NULL array");
+    if (wrench && !optional && (!fext || !g_fext)) return set_err(RB_ERR_NULL, "NULL array");
+    if (g_fext && !fext) return set_err(RB_ERR_ARG, "fd_vjp: g_fext without fext (the plain forward dynamics has no wrench)");
+    const T *out[] = {qdd, g_q, g_qd, g_tau, g_fext};
+    for (int a = 0; a < 5; ++a) {
+        if (!out[a]) continue;
+        for (const T *i : {q, qd, tau, fext, w})
+            if (out[a] == i) return set_err(RB_ERR_ARG, "fd_vjp: an output array is also an input");
+        for (int b = 0; b < a; ++b)
+            if (out[a] == out[b]) return set_err(RB_ERR_ARG, "fd_vjp: two outputs are the same array");
+    }
+    return RB_OK;
+}
+
+// wrench = false: multibody_fd_vjp_plain_batch_* (fext, g_fext NULL)
+template <typename T>
+int fd_vjp_batch(const Multibody *mb, bool wrench, const T *q, const T *qd, const T *tau, const T *fext, const T *w,
+                 T *qdd, T *g_q, T *g_qd, T *g_tau, T *g_fext, int64_t batch, int64_t ld, void *stream) {
+    if (!wrench) {  // the plain family has no wrench arrays: the kernel is chosen by the family alone
+        fext = nullptr;
+        g_fext = nullptr;
+    }
+    auto args_ok = [&] { return fd_vjp_args_ok<T>(wrench, false, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext); };
+    return batch_call<T>(mb, batch, ld, false, args_ok, "fd_vjp launch", [&](const T *, ChunkAt at, uint32_t nb) {
+        const int n = mb->model.n;
+        return launch_fd_vjp<T>(mb, wrench, at(q, n), at(qd, n), at(tau, n), at(fext, 6 * n), at(w, n), at(qdd, n),
+                                at(g_q, n), at(g_qd, n), at(g_tau, n), at(g_fext, 6 * n), nb, ld, (hipStream_t)stream);
+    });
+}
+
 // RB_ERR_UNSUPPORTED (with the condition that failed) when `kind` has no kernel for this model.
 int deriv_supported(const Multibody *mb, rbamd::JitKind kind) {
     const std::string why = rbamd::jit_kind_unsupported(mb->model, kind);
@@ -1026,6 +1077,23 @@ int rnea_vjp_host(const Multibody *mb, bool wrench, const T *q, const T *qd, con
     });
 }
 
+// wrench = false: multibody_fd_vjp_plain_batch_host_* (fext, g_fext NULL)
+template <typename T>
+int fd_vjp_host(const Multibody *mb, bool wrench, const T *q, const T *qd, const T *tau, const T *fext, const T *w,
+                T *qdd, T *g_q, T *g_qd, T *g_tau, T *g_fext, int64_t batch) {
+    const int64_t n = mb ? mb->model.n : 0;
+    auto check = [&] { return fd_vjp_args_ok<T>(wrench, false, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext); };
+    if (!wrench)
+        return host_call_rows<T, 4, 4>(mb, {q, qd, tau, w}, {n, n, n, n}, {qdd, g_q, g_qd, g_tau}, {n, n, n, n}, 0, false,
+                                       batch, check, [&](T **i, T **o, hipStream_t s) {
+            return fd_vjp_batch<T>(mb, false, i[0], i[1], i[2], nullptr, i[3], o[0], o[1], o[2], o[3], nullptr, batch, batch, s);
+        });
+    return host_call_rows<T, 5, 5>(mb, {q, qd, tau, fext, w}, {n, n, n, 6 * n, n}, {qdd, g_q, g_qd, g_tau, g_fext},
+                                   {n, n, n, n, 6 * n}, 0, false, batch, check, [&](T **i, T **o, hipStream_t s) {
+        return fd_vjp_batch<T>(mb, true, i[0], i[1], i[2], i[3], i[4], o[0], o[1], o[2], o[3], o[4], batch, batch, s);
+    });
+}
+
 template <typename T>
 int link_pose_host(const Multibody *mb, const T *q, T *pos, T *rot, int64_t batch) {
     const int64_t n = mb ? mb->model.n : 0;
@@ -1385,6 +1453,8 @@ int check_ext_query(const Multibody *mb, int64_t batch) {
 int ext_kind(int fd) { return (int)(fd ? rbamd::JitKind::FdExt : rbamd::JitKind::RneaExt); }
 // ... nor the inverse dynamics' gradient (check_ext_query's checks): ext selects the wrench form.
 int rnea_vjp_kind(int ext) { return (int)(ext ? rbamd::JitKind::RneaVjpExt : rbamd::JitKind::RneaVjp); }
+// ... nor the forward dynamics' gradient (check_ext_query's checks): ext selects the wrench form.
+int fd_vjp_kind(int ext) { return (int)(ext ? rbamd::JitKind::FdVjpExt : rbamd::JitKind::FdVjp); }
 // ... nor the link-kinematics kernels (check_ext_query's checks): vel selects link_vel (else link_pose).
 int link_kin_kind(int vel) { return (int)(vel ? rbamd::JitKind::LinkVel : rbamd::JitKind::LinkPose); }
 
@@ -1489,6 +1559,15 @@ int multibody_rnea_vjp_jit_source(const Multibody *mb, int ext, int f64, int64_t
 int64_t multibody_rnea_vjp_jit_compile(const Multibody *mb, int ext, int f64, int64_t batch, const char *arch) {
     if (int rc = check_ext_query(mb, batch)) return -rc;
     return compile_query(mb, rnea_vjp_kind(ext), f64, batch, 0, arch);
+}
+
+int multibody_fd_vjp_jit_source(const Multibody *mb, int ext, int f64, int64_t batch, char *buf, int64_t cap) {
+    return source_query(mb, check_ext_query(mb, batch), fd_vjp_kind(ext), f64, batch, 0, buf, cap);
+}
+
+int64_t multibody_fd_vjp_jit_compile(const Multibody *mb, int ext, int f64, int64_t batch, const char *arch) {
+    if (int rc = check_ext_query(mb, batch)) return -rc;
+    return compile_query(mb, fd_vjp_kind(ext), f64, batch, 0, arch);
 }
 
 int multibody_link_kin_jit_source(const Multibody *mb, int vel, int f64, int64_t batch, char *buf, int64_t cap) {
@@ -1920,6 +1999,45 @@ int multibody_rnea_vjp(const Multibody *mb, const double *q, const double *qd, c
                                            "entry points)");
     if (!rbamd::host_rnea_vjp(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext))
         return set_err(RB_ERR_UNSUPPORTED, "rnea_vjp: the single-configuration form runs on the host and needs an FMA3 / "
+                                           "AVX2 CPU");
+    return RB_OK;
+}
+
+// ------------------------------------------- reverse-mode gradient of the forward dynamics
+#define RB_FD_VJP_ENTRY(T, sfx)                                                                                          \
+    int multibody_fd_vjp_batch_##sfx(const Multibody *mb, const T *q, const T *qd, const T *tau, const T *fext,          \
+                                     const T *w, T *qdd, T *g_q, T *g_qd, T *g_tau, T *g_fext, int64_t batch,            \
+                                     int64_t ld, void *stream) {                                                         \
+        return fd_vjp_batch<T>(mb, true, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext, batch, ld, stream);         \
+    }                                                                                                                    \
+    int multibody_fd_vjp_batch_host_##sfx(const Multibody *mb, const T *q, const T *qd, const T *tau, const T *fext,     \
+                                          const T *w, T *qdd, T *g_q, T *g_qd, T *g_tau, T *g_fext, int64_t batch) {     \
+        return fd_vjp_host<T>(mb, true, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext, batch);                      \
+    }                                                                                                                    \
+    int multibody_fd_vjp_plain_batch_##sfx(const Multibody *mb, const T *q, const T *qd, const T *tau, const T *w,       \
+                                           T *qdd, T *g_q, T *g_qd, T *g_tau, int64_t batch, int64_t ld,                 \
+                                           void *stream) {                                                               \
+        return fd_vjp_batch<T>(mb, false, q, qd, tau, nullptr, w, qdd, g_q, g_qd, g_tau, nullptr, batch, ld, stream);    \
+    }                                                                                                                    \
+    int multibody_fd_vjp_plain_batch_host_##sfx(const Multibody *mb, const T *q, const T *qd, const T *tau, const T *w,  \
+                                                T *qdd, T *g_q, T *g_qd, T *g_tau, int64_t batch) {                      \
+        return fd_vjp_host<T>(mb, false, q, qd, tau, nullptr, w, qdd, g_q, g_qd, g_tau, nullptr, batch);                 \
+    }
+RB_FD_VJP_ENTRY(float, f32)
+RB_FD_VJP_ENTRY(double, f64)
+#undef RB_FD_VJP_ENTRY
+
+// Single configuration, fp64, on the calling thread (host_eval.cpp): multibody_rnea_vjp's scope.
+int multibody_fd_vjp(const Multibody *mb, const double *q, const double *qd, const double *tau, const double *fext,
+                     const double *w, double *qdd, double *g_q, double *g_qd, double *g_tau, double *g_fext) {
+    if (!mb) return set_err(RB_ERR_NULL, "NULL Multibody handle");
+    if (int rc = fd_vjp_args_ok<double>(true, true, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext)) return rc;
+    if (!mb->model.serial_revolute())
+        return set_err(RB_ERR_UNSUPPORTED, "fd_vjp: the single-configuration form evaluates serial revolute chains only "
+                                           "(kinematic trees, prismatic joints and a floating base take the batched "
+                                           "entry points)");
+    if (!rbamd::host_fd_vjp(mb->model, mb->pk64.data(), mb->ra64.data(), q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext))
+        return set_err(RB_ERR_UNSUPPORTED, "fd_vjp: the single-configuration form runs on the host and needs an FMA3 / "
                                            "AVX2 CPU");
     return RB_OK;
 }

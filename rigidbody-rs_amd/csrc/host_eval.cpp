@@ -26,6 +26,7 @@
 #include "link_kin_body.hip.hpp"
 #include "rnea_body.hip.hpp"
 #include "rnea_vjp_body.hip.hpp"
+#include "fd_vjp_body.hip.hpp"
 
 namespace rbamd {
 namespace {
@@ -458,6 +459,51 @@ RB_HOST_FMA bool rnea_vjp_fma(int n, const double *mdl, const double *ra, const 
     }
 }
 
+// fext NULL: the gradient without wrench rows (g_fext unused); g_fext NULL: not evaluated.  The forward
+// stage takes fd_ext_fma_n's form: the mass-matrix form up to kHostFdDerivMaxLinks links, the ABA beyond.
+template <int N>
+RB_HOST_FMA bool fd_vjp_fma_n(const double *mdl, const double *ra, const double *q, const double *qd, const double *tau,
+                              const double *fext, const double *w, double *qdd, double *g_q, double *g_qd,
+                              double *g_tau, double *g_fext) {
+    double a[N], b[N];
+    for (int j = 0; j < N; ++j) {
+        a[j] = q[j];
+        b[j] = qd[j];
+    }
+    auto fx = [&](int r) { return fext[r]; };
+    auto tw = [&](double(&tv)[N], double(&wv)[N]) {
+        for (int j = 0; j < N; ++j) {
+            tv[j] = tau[j];
+            wv[j] = w[j];
+        }
+    };
+    auto oqdd = [&](int j, double v) { qdd[j] = v; };
+    auto oq = [&](int j, double v) { g_q[j] = v; };
+    auto oqd = [&](int j, double v) { g_qd[j] = v; };
+    auto ot = [&](int j, double v) { g_tau[j] = v; };
+    auto of = [&](int r, double v) { g_fext[r] = v; };
+    constexpr bool fdh = N <= kHostFdDerivMaxLinks;
+    if (fext)
+        dev::fd_vjp_eval<double, N, false, HostSerialTopo<N>, true, fdh>(mdl, ra, a, b, fx, tw, g_fext != nullptr, oqdd, oq,
+                                                                         oqd, ot, of);
+    else
+        dev::fd_vjp_eval<double, N, false, HostSerialTopo<N>, false, fdh>(mdl, ra, a, b, fx, tw, false, oqdd, oq, oqd, ot,
+                                                                          of);
+    return true;
+}
+
+RB_HOST_FMA bool fd_vjp_fma(int n, const double *mdl, const double *ra, const double *q, const double *qd,
+                            const double *tau, const double *fext, const double *w, double *qdd, double *g_q,
+                            double *g_qd, double *g_tau, double *g_fext) {
+    switch (n) {
+#define X(N) \
+    case N: return fd_vjp_fma_n<N>(mdl, ra, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext);
+        RB_FOR_EACH_DOF(X)
+#undef X
+        default: return false;
+    }
+}
+
 }  // namespace
 
 bool host_fma_available() {
@@ -524,6 +570,12 @@ bool host_rnea_vjp(const Model &m, const double *pk, const double *ra, const dou
                    const double *qdd, const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
                    double *g_fext) {
     return host_eval_supported(m) && rnea_vjp_fma(m.n, pk, ra, q, qd, qdd, fext, w, g_q, g_qd, g_qdd, g_fext);
+}
+
+bool host_fd_vjp(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                 const double *tau, const double *fext, const double *w, double *qdd, double *g_q, double *g_qd,
+                 double *g_tau, double *g_fext) {
+    return host_eval_supported(m) && fd_vjp_fma(m.n, pk, ra, q, qd, tau, fext, w, qdd, g_q, g_qd, g_tau, g_fext);
 }
 
 bool host_link_pose(const Model &m, const double *pk, const double *ra, const double *q, double *pos, double *rot) {

@@ -48,6 +48,13 @@ bool host_rnea_vjp(const Model &m, const double *pk, const double *ra, const dou
                    const double *qdd, const double *fext, const double *w, double *g_q, double *g_qd, double *g_qdd,
                    double *g_fext);
 
+// Reverse-mode gradient of host_fd_ext (fd_vjp_body.hip.hpp) for the cotangent w [n] of qdd: qdd (host_fd_ext's
+// own, from the shared factorisation), g_q, g_qd, g_tau [n], g_fext [6 n] (NULL: not evaluated).  fext NULL:
+// the gradient of the forward dynamics without wrenches, g_fext unused.
+bool host_fd_vjp(const Model &m, const double *pk, const double *ra, const double *q, const double *qd,
+                 const double *tau, const double *fext, const double *w, double *qdd, double *g_q, double *g_qd,
+                 double *g_tau, double *g_fext);
+
 // Kinematics of every link in its URDF link frame (link_kin_body.hip.hpp): pos [3 n] and rot [9 n]
 // (link j's R_j column-major, x_base = R_j x_link), vel [6 n] (link j's linear, then angular
 // velocity, in its own frame); ra = Model::axis_frames().

@@ -50,7 +50,7 @@ int jit_nt(JitKind kind) {
     if (kind == JitKind::Rnea || kind == JitKind::RneaExt || kind == JitKind::RneaVjp || kind == JitKind::RneaVjpExt)
         return tuning().rnea_nt < 0 ? 3 : (tuning().rnea_nt & 3);
     if (kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd || kind == JitKind::FdExt ||
-        kind == JitKind::RolloutContact)
+        kind == JitKind::RolloutContact || kind == JitKind::FdVjp || kind == JitKind::FdVjpExt)
         return tuning().fd_nt & 3;
     // CRBA, fwd_kin, jac, link_pose / link_vel, contact_wrench and cmm (output-bound, as jac)
     if (kind == JitKind::Com || kind == JitKind::Centroidal) return tuning().kin_nt >= 0 ? tuning().kin_nt & 3 : 3;  // as fwd_kin
@@ -372,6 +372,9 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     const bool cz = kind == JitKind::Com || kind == JitKind::Centroidal || kind == JitKind::Cmm;
     // the inverse dynamics' reverse-mode gradient (rnea_vjp_body.hip.hpp), without / with wrench rows
     const bool rvjp = kind == JitKind::RneaVjp || kind == JitKind::RneaVjpExt;
+    // the forward dynamics' reverse-mode gradient (fd_vjp_body.hip.hpp), without / with wrench rows: built
+    // as FdExt is (the same link-force form and forward-dynamics form), so its qdd is that kernel's
+    const bool fvjp = kind == JitKind::FdVjp || kind == JitKind::FdVjpExt;
     if ((deriv || vjp || contact || cz) && !jit_kind_unsupported(m, kind).empty()) return "";
     std::vector<double> pk = m.pack_f64();
     for (int i = 0; i < m.n; ++i) {
@@ -414,7 +417,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
     // 131 instead of 125 VGPRs (3 waves/SIMD instead of 4), and all its grid forms (pairs,
     // single tail, one per lane below 2^19) must stay bit-identical to each other.
     const bool dyn = kind == JitKind::Rnea || kind == JitKind::Fd || kind == JitKind::Rollout || kind == JitKind::RneaFd ||
-                     deriv || vjp || ext || kind == JitKind::RolloutContact;
+                     deriv || vjp || ext || fvjp || kind == JitKind::RolloutContact;
     // jit_variant bit 16384 (A/B): the centre-of-mass form for the fp64 RNEA too
     // rnea_lane_rev: the fp64 RNEA of serial chains longer than 8 links, whose per-link forces
     // hold one wave per SIMD (12 links 264 VGPRs, 30 links 496) and do not fit LDS either
@@ -496,6 +499,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
           : contact                                         ? "#include \"contact_body.hip.hpp\"\n"
           : cz                                              ? "#include \"centroidal_body.hip.hpp\"\n"
           : rvjp                                            ? "#include \"rnea_vjp_body.hip.hpp\"\n"
+          : fvjp                                            ? "#include \"fd_vjp_body.hip.hpp\"\n"
           : lk                                              ? "#include \"link_kin_body.hip.hpp\"\n"
           : ext                                             ? "#include \"ext_body.hip.hpp\"\n"
           : vjp                                            ? "#include \"rollout_vjp_body.hip.hpp\"\n"
@@ -537,7 +541,7 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
         for (size_t k = 0; k < pk.size(); ++k) o << "  " << literal(pk[k], f64) << ",\n";
     }
     o << "};\n";
-    if (ext || lk || contact || rvjp) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
+    if (ext || lk || contact || rvjp || fvjp) {  // every link's axis frame R_a (model.cpp axis_frames): the identity for z-axis links
         const std::vector<double> ra = m.axis_frames();
         o << "static __device__ constexpr T kExtRa[" << ra.size() << "] = {\n";
         for (size_t k = 0; k < ra.size(); ++k) o << "  " << literal(snap(ra[k]), f64) << ",\n";
@@ -705,6 +709,17 @@ std::string jit_source(const Model &m, const JitVariant &v, int waves_req) {
           << ">(kModel, kExtRa, q + o, qd + o, qdd + o, " << (wr ? "fext + o" : "nullptr")
           << ", w + o, g_q + o, g_qd + o, g_qdd + o, " << (wr ? "g_fext + o" : "nullptr")
           << ", threadIdx.x, ld);\n}\n";
+    } else if (fvjp) {
+        // one configuration per lane on SoA rows, as the inverse dynamics' gradient above; qdd is an output
+        const bool wr = kind == JitKind::FdVjpExt;
+        sig(std::string("const T *__restrict__ q, const T *__restrict__ qd, const T *__restrict__ tau, ") +
+            (wr ? "const T *__restrict__ fext, " : "") +
+            "const T *__restrict__ w, T *__restrict__ qdd, T *__restrict__ g_q, T *__restrict__ g_qd, "
+            "T *__restrict__ g_tau, " + (wr ? "T *__restrict__ g_fext, " : "") + "uint32_t B, int64_t ld, int64_t bs");
+        o << lane_prologue << "  rbamd::dev::fd_vjp_lane<T, N, " << F << ", Topo, " << (wr ? "true" : "false") << ", "
+          << (jit_fd_form(m) == 2 ? "true" : "false") << ">(kModel, kExtRa, q + o, qd + o, tau + o, "
+          << (wr ? "fext + o" : "nullptr") << ", w + o, qdd + o, g_q + o, g_qd + o, g_tau + o, "
+          << (wr ? "g_fext + o" : "nullptr") << ", threadIdx.x, ld);\n}\n";
     } else if (kind == JitKind::ContactWrench) {
         // one configuration per lane on SoA rows: fext [6 N][ld], cforce [3 P][ld]
         sig("const T *__restrict__ q, const T *__restrict__ qd, T *__restrict__ fext, T *__restrict__ cforce, "

@@ -53,12 +53,17 @@ namespace rbamd {
 // RneaVjp / RneaVjpExt: the reverse-mode gradient of the inverse dynamics without / with external link
 // wrenches (rnea_vjp_body.hip.hpp), every model, hipRTC only, one configuration per lane on SoA rows.
 // Internal too: multibody_rnea_vjp_jit_source / _compile.
+// FdVjp / FdVjpExt: the reverse-mode gradient of the forward dynamics without / with external link
+// wrenches (fd_vjp_body.hip.hpp), every model, hipRTC only, one configuration per lane on SoA rows; its
+// forward stage takes the formulation jit_fd_form picks for Fd, as FdExt.  Internal too:
+// multibody_fd_vjp_jit_source / _compile.
 enum class JitKind : int {
     Rnea = 0, Fd = 1, Crba = 2, Rollout = 3, FwdKin = 4, Jac = 5, RneaFd = 6, RneaDeriv = 7, FdDeriv = 8,
     RolloutVjp = 9, RneaExt = 10, FdExt = 11, LinkPose = 12, LinkVel = 13, ContactWrench = 14, RolloutContact = 15,
-    RolloutContactVjp = 16, Com = 17, Centroidal = 18, Cmm = 19, RneaVjp = 20, RneaVjpExt = 21
+    RolloutContactVjp = 16, Com = 17, Centroidal = 18, Cmm = 19, RneaVjp = 20, RneaVjpExt = 21,
+    FdVjp = 22, FdVjpExt = 23
 };
-constexpr int kJitKinds = 22;
+constexpr int kJitKinds = 24;
 constexpr int kJitPublicKinds = 9;
 
 // Why `kind` has no kernel for this model (empty: it has one).  Only the derivative kinds, the

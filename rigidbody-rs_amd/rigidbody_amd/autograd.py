@@ -28,6 +28,10 @@ one Multibody.rnea_batch / rnea_ext_batch launch forward, one Multibody.rnea_vjp
     tau = rnea(mb, q, qd, qdd, fext)                         # [n, B]; fext [6 n, B] or None
     cost = (tau ** 2).sum()
     cost.backward()                                          # q.grad, qd.grad, qdd.grad, fext.grad
+
+`fd(mb, q, qd, tau, fext=None)` is the forward dynamics qdd [n, B] in the same way, on every model: one
+Multibody.fd_batch / fd_ext_batch launch forward, one Multibody.fd_vjp_batch launch backward
+(rigidbody_batch.h "reverse-mode gradient of the forward dynamics").
 """
 import torch
 
@@ -96,3 +100,28 @@ def rnea(mb, q, qd, qdd, fext=None):
     and fext [6 n, B], fp32 or fp64 (the inputs are not modified), differentiable with respect to every
     tensor argument; an input without requires_grad gets None."""
     return _Rnea.apply(mb, q, qd, qdd, fext)
+
+
+class _Fd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mb, q, qd, tau, fext):
+        ins = [t.detach().contiguous() for t in (q, qd, tau)]
+        f = None if fext is None else fext.detach().contiguous()
+        qdd = mb.fd_batch(*ins) if f is None else mb.fd_ext_batch(*ins, f)
+        ctx.mb, ctx.ext = mb, f is not None
+        ctx.save_for_backward(*ins, *([f] if f is not None else []))
+        return qdd
+
+    @staticmethod
+    def backward(ctx, grad_qdd):
+        saved = ctx.saved_tensors
+        g = ctx.mb.fd_vjp_batch(*saved[:3], grad_qdd.contiguous(), fext=saved[3] if ctx.ext else None)
+        g = list(g[1:]) + ([] if ctx.ext else [None])  # (the launch's own qdd is not needed here)
+        return (None, *[x if need else None for x, need in zip(g, ctx.needs_input_grad[1:])])
+
+
+def fd(mb, q, qd, tau, fext=None):
+    """qdd = fd_ext(q, qd, tau, fext) [n, B] (fext=None: the plain forward dynamics) of CUDA tensors q, qd, tau
+    [n, B] and fext [6 n, B], fp32 or fp64 (the inputs are not modified), differentiable with respect to every
+    tensor argument; an input without requires_grad gets None."""
+    return _Fd.apply(mb, q, qd, tau, fext)

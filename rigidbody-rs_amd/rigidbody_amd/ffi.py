@@ -106,6 +106,11 @@ _SIGNATURES = {
     "multibody_rnea_vjp": (_int, [_vp] + [_dp] * 9),
     "multibody_rnea_vjp_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
     "multibody_rnea_vjp_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
+    # reverse-mode gradient of the forward dynamics: one configuration (handle, q, qd, tau, fext, w, qdd,
+    # g_q, g_qd, g_tau, g_fext); inspection (handle, ext, f64, batch, ...)
+    "multibody_fd_vjp": (_int, [_vp] + [_dp] * 10),
+    "multibody_fd_vjp_jit_source": (_int, [_vp, _int, _int, _i64, _str, _i64]),
+    "multibody_fd_vjp_jit_compile": (_i64, [_vp, _int, _int, _i64, _str]),
     # kinematics of every link: one configuration (handle, q, pos, rot) / (handle, q, qd, vel);
     # inspection (handle, vel, f64, batch, ...)
     "multibody_link_pose": (_int, [_vp] + [_dp] * 3),
@@ -135,12 +140,12 @@ _SIGNATURES = {
 # batched entry points: (handle, arrays..., batch[, ld][, stream]) by their number of arrays
 _ARRAYS = {"rnea": 4, "fd": 4, "rnea_fd": 6, "crba": 2, "fwd_kin": 2, "jac": 2, "rnea_deriv": 5, "fd_deriv": 7,
            "rnea_ext": 5, "fd_ext": 5, "link_pose": 3, "link_vel": 3, "contact_wrench": 4, "com": 2, "centroidal": 5,
-           "cmm": 2, "rnea_vjp": 9, "rnea_vjp_plain": 7}
+           "cmm": 2, "rnea_vjp": 9, "rnea_vjp_plain": 7, "fd_vjp": 10, "fd_vjp_plain": 8}
 for _t in ("f32", "f64"):
     for _k, _n in _ARRAYS.items():
         _SIGNATURES[f"multibody_{_k}_batch_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _i64, _vp])
         if not _k.endswith(("_deriv", "_ext")) and not _k.startswith(("link_", "contact_", "com", "centroidal", "cmm",
-                                                                      "rnea_vjp")):
+                                                                      "rnea_vjp", "fd_vjp")):
             _SIGNATURES[f"multibody_{_k}_batch_tiled_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64, _vp])
         if _k not in ("crba", "fwd_kin", "jac"):
             _SIGNATURES[f"multibody_{_k}_batch_host_{_t}"] = (_int, [_vp] * (1 + _n) + [_i64])
@@ -644,6 +649,78 @@ class Multibody:
         rows = [self.n] * 3 + ([6 * self.n] if fext is not None else [])
         outs = [np.empty((r, B), dtype=arrs[0].dtype) for r in rows]
         kind = "rnea_vjp" if fext is not None else "rnea_vjp_plain"
+        fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
+        _check(fn(self._h, *[a.ctypes.data for a in (*ins, *outs)], B), f"{kind}_batch_host")
+        return tuple(outs)
+
+    # ---- reverse-mode gradient of the forward dynamics (rigidbody_batch.h has the definitions)
+    def fd_vjp(self, q, qd, tau, w, fext=None):
+        """multibody_fd_vjp: (qdd, g_q, g_qd, g_tau [n][, g_fext [n, 6]]), qdd = fd_ext(q, qd, tau, fext) -- fext=None:
+        without wrenches -- and the gradient of w . qdd, of one configuration, on the calling thread."""
+        q, qd, tau, w = (_dvec(x, self.n) for x in (q, qd, tau, w))
+        outs = [np.empty(self.n) for _ in range(4)]
+        gf = None
+        if fext is not None:
+            fext = _dvec(np.asarray(fext, dtype=np.float64).reshape(-1), 6 * self.n)
+            gf = np.empty(6 * self.n)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_dp)
+        _check(_lib.multibody_fd_vjp(self._h, *[ptr(a) for a in (q, qd, tau, fext, w, *outs, gf)]), "fd_vjp")
+        return (*outs, gf.reshape(self.n, 6)) if gf is not None else tuple(outs)
+
+    def fd_vjp_jit_source(self, ext=False, f64=False, batch=1 << 20) -> str:
+        """hipRTC source of the fd_vjp kernel without (ext=False) / with wrench rows
+        (multibody_fd_vjp_jit_source)."""
+        a = (self._h, int(bool(ext)), int(bool(f64)), int(batch))
+        n = _lib.multibody_fd_vjp_jit_source(*a, None, 0)
+        if n < 0:
+            raise RigidBodyError(last_error())
+        buf = ctypes.create_string_buffer(n + 1)
+        _lib.multibody_fd_vjp_jit_source(*a, buf, n + 1)
+        return buf.value.decode()
+
+    def fd_vjp_jit_compile(self, ext=False, f64=False, arch="gfx950", batch=1 << 20) -> int:
+        r = _lib.multibody_fd_vjp_jit_compile(self._h, int(bool(ext)), int(bool(f64)), int(batch), arch.encode())
+        if r < 0:
+            raise RigidBodyError(last_error())
+        return r
+
+    def fd_vjp_batch(self, q, qd, tau, w, fext=None, stream=None):
+        """multibody_fd_vjp_batch_* (fext [6 n, B]) / multibody_fd_vjp_plain_batch_* (fext=None): q, qd, tau,
+        w [n, B] -> (qdd, g_q, g_qd, g_tau [n, B][, g_fext [6 n, B]]): the forward dynamics and the gradient
+        of sum_i w_i qdd_i per configuration, one launch; rows of g_fext as those of fext."""
+        q = _soa(q, self.n, "q")
+        if q.dtype not in _TORCH_SUFFIX:
+            raise TypeError(f"q has dtype {q.dtype}, expected float32 or float64")
+        B = q.shape[1]
+        ins = [q] + [_soa(t, self.n, name, q.dtype, B) for t, name in ((qd, "qd"), (tau, "tau"))]
+        if fext is not None:
+            ins.append(_soa(fext, 6 * self.n, "fext", q.dtype, B))
+        ins.append(_soa(w, self.n, "w", q.dtype, B))
+        rows = [self.n] * 4 + ([6 * self.n] if fext is not None else [])
+        outs = [torch.empty((r, _ld(q)), dtype=q.dtype, device=q.device)[:, :B] for r in rows]
+        live = ins + outs
+        ld = _same_ld(live)
+        dev = _one_device(live)
+        kind = "fd_vjp" if fext is not None else "fd_vjp_plain"
+        fn = getattr(_lib, f"multibody_{kind}_batch_{_TORCH_SUFFIX[q.dtype]}")
+        with torch.cuda.device(dev):
+            _check(fn(self._h, *[t.data_ptr() for t in live], B, ld, _stream_ptr(stream, dev)), f"{kind}_batch")
+        return tuple(outs)
+
+    def fd_vjp_batch_host(self, q, qd, tau, w, fext=None, dtype=np.float64):
+        """Blocking host form of fd_vjp_batch on numpy arrays."""
+        arrs = _host_soa((q, qd, tau, w), self.n, dtype)
+        B = arrs[0].shape[1]
+        ins = list(arrs[:3])
+        if fext is not None:
+            fext = np.ascontiguousarray(fext, dtype=arrs[0].dtype)
+            if fext.shape != (6 * self.n, B):
+                raise ValueError(f"fext must be [{6 * self.n}, {B}], got {fext.shape}")
+            ins.append(fext)
+        ins.append(arrs[3])
+        rows = [self.n] * 4 + ([6 * self.n] if fext is not None else [])
+        outs = [np.empty((r, B), dtype=arrs[0].dtype) for r in rows]
+        kind = "fd_vjp" if fext is not None else "fd_vjp_plain"
         fn = getattr(_lib, f"multibody_{kind}_batch_host_{'f32' if arrs[0].dtype == np.float32 else 'f64'}")
         _check(fn(self._h, *[a.ctypes.data for a in (*ins, *outs)], B), f"{kind}_batch_host")
         return tuple(outs)
